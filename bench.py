@@ -16,6 +16,10 @@ scaling; time = max over ranks between two barriers.  Rank 0 prints ONE JSON lin
 inter-step patch split, six 1024^2 windows per step sharded over the N ranks with one RCCL all-gather per step
 (strong scaling: the image is fixed, N grows).  ``--latency`` adds B = 1 numbers (HIP-graph replay) at 256^2 and at the
 ``DDPM.test`` size (384^2 padded input, UNet at 416^2) to the JSON line under "latency".
+
+``--dump-outputs DIR`` writes what the last timed step returned (the restored batch, or the restored padded image in patch
+mode) as ``DIR/restored.npy`` in float32 after the timed region.  Every step restores the same inputs with the same noise, so
+two builds run with the same arguments can be compared output for output, whatever --steps and --warmup are.
 """
 import argparse
 import ctypes
@@ -174,6 +178,19 @@ def roofline_record(rows, whole_tflops=None, sustained=None):
     return roof
 
 
+DUMP_BYTES = 60 << 20          # with the .npy header still under 64 MB (10^6 or 2^20 bytes)
+
+
+def dump_output(out_dir, name, t):
+    """``out_dir/<name>.npy`` in float32; above DUMP_BYTES a fixed seeded sample of the flattened elements (sorted indices),
+    the same for every run of the same shape."""
+    a = t.detach().float().cpu().numpy()
+    if a.nbytes > DUMP_BYTES:
+        a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, DUMP_BYTES // 4, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def latency_leg(net, dev, T):
     """B = 1 restorations with the forward replayed from a HIP graph: 256^2 (UNet at 288^2) and the DDPM.test size
     (256^2 crop reflect-padded by 64 -> 384^2 input, UNet at 416^2; the reference's val loader is batch_size = 1)."""
@@ -215,7 +232,10 @@ def main():
     ap.add_argument("--patch-batch", type=int, default=0, help="patch mode: windows per engine call (0 = the module's default)")
     ap.add_argument("--height", type=int, default=1424)
     ap.add_argument("--width", type=int, default=2128)
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's output to DIR/restored.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -250,7 +270,11 @@ def main():
         return patch_mode(args, net, dev, dist, rank, world, T)
     B, S = args.batch, args.size
     cond = torch.from_numpy(synth_inputs(B, S, S, seed=rank)[0]).to(dev)
-    torch.manual_seed(1 + rank)
+
+    def restore():
+        # each restoration takes its noise seed from torch's CPU generator: reseeded, every step draws the same noise
+        torch.manual_seed(1 + rank)
+        return net.super_resolution(cond, False)
 
     # bracket the GEMM-core launches of ONE forward per restoration with HIP events (roofline leg)
     L = ulib.load()
@@ -276,13 +300,13 @@ def main():
 
     with torch.no_grad():
         for _ in range(args.warmup):
-            net.super_resolution(cond, False)
+            restore()
         prof = LaunchProfile(L, ulib)
         prof.read()                                            # drop warm-up profile rows
         sync()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            out = net.super_resolution(cond, False)
+            out = restore()
         sync()
         t1 = time.perf_counter()
     elapsed = torch.tensor([t1 - t0], dtype=torch.float64, device=dev)
@@ -290,6 +314,8 @@ def main():
         dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
     elapsed = float(elapsed.item())
     assert torch.isfinite(out).all()
+    if args.dump_outputs and rank == 0:
+        dump_output(args.dump_outputs, "restored", out)
 
     rows = prof.read()
 
@@ -374,6 +400,8 @@ def patch_mode(args, net, dev, dist, rank, world, T):
         dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
     elapsed = float(elapsed.item())
     assert torch.isfinite(out).all()
+    if args.dump_outputs and rank == 0:
+        dump_output(args.dump_outputs, "restored", out)
     # self-explaining scaling line: windows this rank evaluates per step and what the collective costs per step
     per = (nwin + world - 1) // world
     mine = max(0, min(per, nwin - rank * per))

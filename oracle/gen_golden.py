@@ -81,6 +81,35 @@ def extra_full_config(net):
                         eps_crop=e[0, :, 100:132, 60:92].numpy(), eps_ds=e[0, :, ::8, ::8].numpy())
 
 
+def tiny_vs_reference(net):
+    """Fixture of tests/test_oracle_vs_reference.py (tiny config): forward + predictor at B = 2, the strided sampler and the
+    50-step p_sample_loop with every snapshot.  The test replays the samplers' noise from the same torch seeds; the float64
+    sum of each sampler's draws is stored so that a changed generator shows up as such instead of as a numerical mismatch."""
+    from ucdir_amd.weights import synth_inputs
+    rec = {}
+    cond, guide, x_t = map(torch.from_numpy, synth_inputs(2, 40, 56, seed=31))
+    lvl = torch.tensor([[0.1], [0.8]])
+    rec["fwd_level"] = lvl.numpy()
+    rec["fwd_eps"] = net.denoise_fn(torch.cat([cond, x_t], 1), lvl, guide=guide).numpy()
+    rec["fwd_predictor"] = net.predictor(cond).numpy()
+
+    net.set_new_noise_schedule(SCHED50, torch.device("cpu"))
+    cond, guide, _ = map(torch.from_numpy, synth_inputs(1, 48, 40, seed=32))
+    torch.manual_seed(11)
+    st = torch.get_rng_state()
+    rec["ddim_out"] = net.ddim_sample(cond, False, kwargs={"guide": guide}).numpy()
+    torch.set_rng_state(st)
+    rec["ddim_noise_sum"] = np.stack([torch.randn(cond.shape).numpy() for _ in range(6)]).sum(dtype=np.float64)
+
+    cond = torch.from_numpy(synth_inputs(1, 40, 40, seed=33)[0])
+    torch.manual_seed(12)
+    st = torch.get_rng_state()
+    rec["loop_out"] = net.super_resolution(cond, True).numpy()
+    torch.set_rng_state(st)
+    rec["loop_noise_sum"] = np.stack([torch.randn(cond.shape).numpy() for _ in range(50)]).sum(dtype=np.float64)
+    np.savez_compressed(os.path.join(OUT, "tiny_vs_reference.npz"), **rec)
+
+
 def main():
     from ucdir_amd.weights import synth_inputs
     os.makedirs(OUT, exist_ok=True)
@@ -89,6 +118,9 @@ def main():
     if "--extra-only" in sys.argv:           # only the round-3 fixtures (the others are unchanged)
         net, cfg, sd = ref_model(networks, {})
         extra_full_config(net)
+        return
+    if "--vs-reference-only" in sys.argv:    # only tests/golden/tiny_vs_reference.npz (the others are unchanged)
+        tiny_vs_reference(ref_model(networks, TINY)[0])
         return
 
     # (iv) schedule tables ----------------------------------------------------------------------
@@ -152,6 +184,7 @@ def main():
                                params={"time": lvl1, "guide": torch.from_numpy(guide)}, skip=128, padding=32)
     np.savez_compressed(os.path.join(OUT, "tiny_patch.npz"), cond=cond, guide=guide, x_t=x_t,
                         level=lvl1.numpy(), out=outp.numpy())
+    tiny_vs_reference(net)
 
     # small config (kernel-supported channel counts): forward goldens for the GPU parity tests ----
     net, cfg, sd = ref_model(networks, SMALL)

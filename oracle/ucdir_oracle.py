@@ -8,7 +8,7 @@ where /root/reference does not exist.  Only ``tests/``, ``__graft_entry__.smoke(
 Pinning: ``oracle/gen_golden.py`` imports the real reference (in the build container
 only) and stores its outputs under ``tests/golden/``; ``tests/test_oracle_golden.py``
 checks every function below against those fixtures, and
-``tests/test_oracle_vs_reference.py`` compares live when the reference is present.
+``tests/test_oracle_vs_reference.py`` checks the tiny-config samplers against them.
 The reference itself has no tests or golden vectors, so those
 generated fixtures are the only pins.
 
