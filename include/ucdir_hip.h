@@ -130,6 +130,21 @@ int32_t ucdir_sampler_step_rng_batched(float* x_t, const float* eps, int64_t n, 
                                        float c_recip, float c_recipm1, float coef1, float coef2, float sigma,
                                        const uint64_t* seeds_dev, uint32_t step, void* stream);
 int32_t ucdir_fill_normal_batched(float* x, int64_t n, int64_t per, const uint64_t* seeds_dev, uint32_t step, void* stream);
+/* Fused update of the few-step samplers (DDIM, DPM-Solver++ multistep order 1/2; additive in ABI 5), in place on x (n fp32 elements):
+ *   x0     = c_recip * x - c_recipm1 * eps          (flags & 2: c_recip * (x - c_recipm1 * eps); flags & 1: clamped to [-1, 1])
+ *   x     <- p * x0 + q * x + r * eps + b1 * m_prev + sigma * z
+ *   m_prev <- x0                                    (when store_m != 0)
+ * m_prev is read only when b1 != 0 and may be NULL when b1 == 0 and store_m == 0.  z is the standard normal ucdir_fill_normal /
+ * ucdir_fill_normal_batched draw for (seed, step, element); a non-NULL `noise` (n elements) replaces it; sigma == 0 draws nothing.
+ * Each product and sum is rounded on its own (no FMA contraction).  Every pointer on the device of x and 16-byte aligned.  No
+ * synchronisation and no allocation: the call can be captured in a graph. */
+int32_t ucdir_fewstep_update(float* x, const float* eps, float* m_prev, const float* noise, int64_t n,
+                             float c_recip, float c_recipm1, int32_t flags, float p, float q, float r, float b1, int32_t store_m,
+                             float sigma, uint64_t seed, uint32_t step, void* stream);
+/* The same with per-sample streams: n / per samples of `per` elements (per a multiple of 4), sample b draws from seeds_dev[b]. */
+int32_t ucdir_fewstep_update_batched(float* x, const float* eps, float* m_prev, const float* noise, int64_t n, int64_t per,
+                                     float c_recip, float c_recipm1, int32_t flags, float p, float q, float r, float b1, int32_t store_m,
+                                     float sigma, const uint64_t* seeds_dev, uint32_t step, void* stream);
 /* Window batch of the inter-step patch split (utils/util.py:113-137: F.pad(..., mode='reflect') then one slice per window) in ONE launch,
  * straight from the un-padded canvas: out[(w * B + b)][c][y][x] = x[b][c][refl(h0_w + y - pad)][refl(w0_w + x - pad)], x (B, C, H, W) fp32,
  * out (nwin * B, C, skip, skip) fp32, win_dev = nwin pairs (h0, w0) of int32 ON THE DEVICE in padded coordinates (the window list of

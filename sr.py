@@ -33,7 +33,18 @@ from ucdir_amd import model as Model  # noqa: E402
 from ucdir_amd.data import PairDataset  # noqa: E402
 
 
-def main(argv=None):
+def apply_sampler_flags(opt, args):
+    """--sampler / --sampler-steps / --sampler-order / --ddim-eta override the keys of model.sampler (DDPM.__init__ reads it)."""
+    over = {"name": args.sampler, "steps": args.sampler_steps, "order": args.sampler_order, "eta": args.ddim_eta}
+    over = {k: v for k, v in over.items() if v is not None}
+    if over:
+        spec = dict(opt["model"].get("sampler") or {})
+        spec.update(over)
+        opt["model"]["sampler"] = spec
+    return opt
+
+
+def make_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument("-c", "--config", type=str, default="config/sid.yaml")
     parser.add_argument("-p", "--phase", type=str, choices=["train", "val"], default="val")
@@ -51,7 +62,16 @@ def main(argv=None):
     parser.add_argument("--batch", type=int, default=16,
                         help="restore up to this many same-sized val images per DDPM.test call (1: the reference's one-by-one loop)")
     parser.add_argument("--seed", type=int, default=None, help="base of the per-image noise seeds (default: one random draw per run)")
-    args = parser.parse_args(argv)
+    parser.add_argument("--sampler", choices=["ddpm", "ddim", "dpm_solver++"], default=None,
+                        help="restore with this sampler (overrides model.sampler of the YAML; ddpm: the T-step ancestral sampler)")
+    parser.add_argument("--sampler-steps", type=int, default=None, help="network calls of a ddim / dpm_solver++ restoration")
+    parser.add_argument("--sampler-order", type=int, choices=[1, 2], default=None, help="dpm_solver++ multistep order")
+    parser.add_argument("--ddim-eta", type=float, default=None, help="ddim noise scale (0: deterministic, 1: the reference's setting)")
+    return parser
+
+
+def main(argv=None):
+    args = make_parser().parse_args(argv)
     if args.phase != "val":
         raise SystemExit("only -p val is implemented (sampling path); training is out of scope of this build")
 
@@ -66,6 +86,7 @@ def main(argv=None):
 
     opt = Config.parse(args, world_size=world)
     opt["rank"], opt["world_size"] = rank, world
+    apply_sampler_flags(opt, args)
     logging.basicConfig(level=logging.INFO if rank == 0 else logging.ERROR, format="%(asctime)s %(message)s")
     logger = logging.getLogger("base")
     fh = logging.FileHandler(os.path.join(opt["path"]["log"], "val.log"))

@@ -18,15 +18,46 @@ Differences from the reference, all result-preserving:
     the denoiser sees the same pointers every step (HIP-graph replay, ``DY3h.set_graph``);
   * ``noise_seed``: when set, x_T and the per-step noise come from a device generator seeded with it at the
     start of every loop - identical on every rank, which the sharded patch split needs (every rank applies
-    the same sampler update to the gathered eps).
+    the same sampler update to the gathered eps; SURVEY.md §8e);
+  * ``sampler`` (``model.sampler`` in the YAML, ``sr.py --sampler``): when set, ``super_resolution`` restores with
+    ``fewstep_sample`` - DDIM or DPM-Solver++ in 5-25 network calls instead of T, the update fused into one HIP kernel
+    (``ucdir_fewstep_update``) on the ancestral path's noise streams, buffers and graph replay.
 """
+from collections import namedtuple
 from functools import partial
 
 import numpy as np
 import torch
 import torch.nn as nn
 
-from .ucdir import UNetSeeInDark, fill_normal_, sampler_step_, sampler_step_rng_
+from . import dpm_solver as D
+from .ucdir import FEWSTEP_CLIP, FEWSTEP_FACTORED, UNetSeeInDark, fewstep_update_, fill_normal_, sampler_step_, sampler_step_rng_
+
+SAMPLERS = ("ddpm", "ddim", "dpm_solver++")
+TIME_INPUTS = ("level", "reference")
+# one network call + one fused update of a few-step sampler: the noise level fed to the network, the coefficients of
+# ucdir_fewstep_update (float64 here, float32 at the kernel boundary) and the noise counter k of the step (0: no noise)
+FewStep = namedtuple("FewStep", "level c_recip c_recipm1 flags p q r b1 store_m sigma k")
+
+
+def parse_sampler(spec):
+    """``model.sampler`` of the YAML -> None (the T-step ancestral sampler) or a complete dict of ``fewstep_sample`` arguments.
+    Absent, empty or ``name: ddpm`` keeps today's path.  Defaults: DDIM 5 steps (the reference's ddim_sampling), DPM-Solver++ 20
+    steps (its dpm_solver driver), order 2, eta 1, the network fed the noise level it is trained on."""
+    if not spec or spec.get("name") == "ddpm":
+        return None
+    if not spec.get("name"):
+        raise ValueError("model.sampler %r has no name (ddpm, ddim or dpm_solver++)" % (dict(spec),))
+    name = spec["name"]
+    if name not in SAMPLERS:
+        raise ValueError("model.sampler.name must be one of %s, got %r" % (", ".join(SAMPLERS), name))
+    def get(key, default):
+        return default if spec.get(key) is None else spec[key]
+    out = {"sampler": name, "steps": int(get("steps", 5 if name == "ddim" else 20)), "order": int(get("order", 2)),
+           "eta": float(get("eta", 1.0)), "time_input": get("time_input", "level")}
+    if out["steps"] < 1 or out["order"] not in (1, 2) or out["eta"] < 0 or out["time_input"] not in TIME_INPUTS:
+        raise ValueError("bad model.sampler %r: steps >= 1, order 1 or 2, eta >= 0, time_input one of %s" % (dict(spec), TIME_INPUTS))
+    return out
 
 
 def make_beta_schedule(schedule, n_timestep, linear_start=1e-4, linear_end=2e-2, cosine_s=8e-3):
@@ -66,6 +97,7 @@ class GaussianDiffusion(nn.Module):
         self.sample_seeds = None     # optional list of ints, one per sample of the NEXT p_sample_loop batch: every sample draws its own
                                      # in-kernel noise stream (counters local to the sample), so an image's noise does not depend on the
                                      # batch it is grouped into (sr.py --batch); ignored when noise is injected (noise_source)
+        self.sampler = None          # optional dict of fewstep_sample arguments (parse_sampler): super_resolution restores with it
         self._gen = None
 
     def set_loss(self, device):
@@ -191,12 +223,37 @@ class GaussianDiffusion(nn.Module):
 
     def _p_sample_steps(self, x, guide, sample_inter):
         self._start_noise(x.device, kernel_rng=True)
+        seeds = self._seeds_tensor(x)
+        cond, img, eps_buf, lvl = self._loop_buffers(x, seeds)
+        ret = [x]
+        k = 1
+        for i in reversed(range(self.num_timesteps)):
+            level, c_recip, c_recipm1, coef1, coef2, sigma = self.step_coefficients(i)
+            lvl.fill_(level)
+            eps = self._eps(cond, img, lvl, guide, out=eps_buf)
+            if self.noise_source is not None:
+                noise = self._noise(img, k) if i > 0 else None
+                sampler_step_(img, eps, noise, c_recip, c_recipm1, coef1, coef2, sigma)
+            else:                                             # noise of (seed, step k, element) generated in the update kernel
+                sampler_step_rng_(img, eps, self._kseed, k, c_recip, c_recipm1, coef1, coef2, sigma if i > 0 else 0.0, seeds=seeds)
+            if i > 0:
+                k += 1
+            if i % sample_inter == 0:
+                ret.append(img.clone())
+        return ret
+
+    def _seeds_tensor(self, x):
+        """The per-sample Philox keys of ``sample_seeds`` on the device (None: one stream of ``_kseed``, or injected noise)."""
+        if self.sample_seeds is None or self.noise_source is not None:
+            return None
         B = x.shape[0]
-        seeds = None
-        if self.sample_seeds is not None and self.noise_source is None:
-            if len(self.sample_seeds) != B:
-                raise ValueError("sample_seeds holds %d seeds for a batch of %d" % (len(self.sample_seeds), B))
-            seeds = torch.tensor([int(v) % (2 ** 63) for v in self.sample_seeds], dtype=torch.int64, device=x.device)
+        if len(self.sample_seeds) != B:
+            raise ValueError("sample_seeds holds %d seeds for a batch of %d" % (len(self.sample_seeds), B))
+        return torch.tensor([int(v) % (2 ** 63) for v in self.sample_seeds], dtype=torch.int64, device=x.device)
+
+    def _loop_buffers(self, x, seeds):
+        """(cond, x_t, eps, level) of a sampling loop, x_t holding x_T (step 0 of the noise stream, or the injected noise k = 0)."""
+        B = x.shape[0]
         if getattr(self.denoise_fn, "use_graph", False) and self._small(x):
             # graph replay: the four tensors the denoiser sees live in buffers that persist ACROSS restorations of the
             # same shape, so the forward is captured once and replayed for every step of every image
@@ -220,22 +277,7 @@ class GaussianDiffusion(nn.Module):
                 img = fill_normal_(torch.empty_like(x), self._kseed, 0, seeds=seeds)
             eps_buf = torch.empty_like(img)
             lvl = torch.empty((B, 1), dtype=torch.float32, device=x.device)
-        ret = [x]
-        k = 1
-        for i in reversed(range(self.num_timesteps)):
-            level, c_recip, c_recipm1, coef1, coef2, sigma = self.step_coefficients(i)
-            lvl.fill_(level)
-            eps = self._eps(cond, img, lvl, guide, out=eps_buf)
-            if self.noise_source is not None:
-                noise = self._noise(img, k) if i > 0 else None
-                sampler_step_(img, eps, noise, c_recip, c_recipm1, coef1, coef2, sigma)
-            else:                                             # noise of (seed, step k, element) generated in the update kernel
-                sampler_step_rng_(img, eps, self._kseed, k, c_recip, c_recipm1, coef1, coef2, sigma if i > 0 else 0.0, seeds=seeds)
-            if i > 0:
-                k += 1
-            if i % sample_inter == 0:
-                ret.append(img.clone())
-        return ret
+        return cond, img, eps_buf, lvl
 
     @torch.no_grad()
     def ddim_sample(self, x_in, continous=False, kwargs={}, sampling_timesteps=5, eta=1.0):
@@ -296,6 +338,92 @@ class GaussianDiffusion(nn.Module):
         finally:
             self._end()
 
+    def fewstep_plan(self, sampler, steps, order=2, eta=1.0, time_input="level"):
+        """The per-call table of ``fewstep_sample`` (host, float64): one ``FewStep`` per network call.
+
+        * ``ddim``: the pairs of ``_ddim_steps`` (``linspace(-1, T-1, steps+1).int()``), its level, c_recip / c_recipm1 and its
+          sigma / c arithmetic on the same table values; noise counter k = 1, 2, ... per pair with t_next >= 0.
+        * ``dpm_solver++``: the uniform time grid 1 -> 1/N of ``dpm_solver.sample`` (first step first order, lower order on the last
+          step below 10 steps); x0 = (x - sigma_s eps) / alpha_s (the kernel's factored form), x <- a x + b0 x0 + b1 x0_prev
+          (``dpm_solver.multistep_coefficients``).
+          The network sees the noise level sqrt(abar(s)) = alpha_s (``time_input="level"``: what DY3h is conditioned on, as in every
+          other sampler here) or the reference driver's time index (s - 1/N) * 1000 (``"reference"``, sr.py:141-147)."""
+        if sampler == "ddim":
+            T = self.num_timesteps
+            times = list(reversed(torch.linspace(-1, T - 1, steps=steps + 1).int().tolist()))
+            ac = self._host_tables["alphas_cumprod"]
+            plan, k = [], 1
+            for t, t_next in zip(times[:-1], times[1:]):
+                level, c_recip, c_recipm1, _, _, _ = self.step_coefficients(t)
+                if t_next < 0:
+                    plan.append(FewStep(level, c_recip, c_recipm1, FEWSTEP_CLIP, 1.0, 0.0, 0.0, 0.0, 0, 0.0, 0))
+                    continue
+                a, an = float(ac[t]), float(ac[t_next])
+                sigma = eta * ((1 - a / an) * (1 - an) / (1 - a)) ** 0.5
+                c = (1 - an - sigma ** 2) ** 0.5
+                plan.append(FewStep(level, c_recip, c_recipm1, FEWSTEP_CLIP, an ** 0.5, 0.0, c, 0.0, 0, sigma, k))
+                k += 1
+            return plan
+        if sampler == "dpm_solver++":
+            if order not in (1, 2) or steps < order:
+                raise ValueError("dpm_solver++ needs order 1 or 2 and steps >= order")
+            if time_input not in TIME_INPUTS:
+                raise ValueError("time_input must be one of %s" % (TIME_INPUTS,))
+            ns = D.NoiseScheduleVP(self._host_tables["betas"])             # the betas dpm_solver_sample builds its schedule from
+            ts = [float(v) for v in np.linspace(ns.T, 1.0 / ns.total_N, steps + 1)]
+            plan, t_prev = [], [ts[0]]
+            for step in range(1, steps + 1):
+                s_, t = ts[step - 1], ts[step]
+                o = min(order, step)
+                if steps < 10:
+                    o = min(o, steps + 1 - step)
+                a, b0, b1 = D.multistep_coefficients(ns, t_prev, t, o)
+                alpha, std = ns.marginal_alpha(s_), ns.marginal_std(s_)
+                level = alpha if time_input == "level" else ns.model_input_time(s_)
+                # x0 = (x - sigma_s eps) * fl32(1 / fl32(alpha_s)): one multiply by the fp32 reciprocal
+                inv = float(np.float32(1.0) / np.float32(alpha))
+                plan.append(FewStep(level, inv, std, FEWSTEP_FACTORED, b0, a, 0.0, b1 if o == 2 else 0.0, int(step < steps), 0.0, 0))
+                t_prev = (t_prev + [t])[-2:]
+            return plan
+        raise ValueError("fewstep_sample: sampler must be 'ddim' or 'dpm_solver++', got %r" % (sampler,))
+
+    @torch.no_grad()
+    def fewstep_sample(self, x_in, sampler, steps, order=2, eta=1.0, time_input="level", continous=False, kwargs={}):
+        """DDIM (model/diffusion.py:247-294) or DPM-Solver++ 2M (the reference's dpm_solver driver, sr.py:185-231) in ``steps``
+        network calls, each followed by ONE fused update launch (``ucdir_fewstep_update``).  Same plumbing as ``p_sample_loop``:
+        x_T and DDIM's per-step noise come from the in-kernel Philox streams (``sample_seeds`` / ``noise_seed`` honoured, DDIM
+        noise counter k = 1, 2, ...) or from ``noise_source``; cond / x_t / eps / level live in the persistent buffers graph
+        replay needs, plus one x0-history buffer for DPM-Solver++; images above ``patch_threshold`` take the patch split.
+        ``continous``: dim-0 blocks of B - the input, then x after every call (the final result last), as p_sample_loop."""
+        if not self.conditional:
+            raise NotImplementedError("unconditional sampling is not part of the UCDIR restoration path")
+        plan = self.fewstep_plan(sampler, steps, order, eta, time_input)
+        x = x_in.contiguous().float()
+        self._begin()
+        try:
+            ret = self._fewstep_steps(x, kwargs.get("guide"), plan, continous)
+        finally:
+            self._end()
+        return torch.cat(ret, dim=0) if continous else ret[-1]
+
+    def _fewstep_steps(self, x, guide, plan, continous):
+        self._start_noise(x.device, kernel_rng=True)
+        seeds = self._seeds_tensor(x)
+        cond, img, eps_buf, lvl = self._loop_buffers(x, seeds)
+        m_prev = torch.empty_like(x) if any(s.store_m for s in plan) else None
+        injected = self.noise_source is not None
+        seed = 0 if injected else self._kseed
+        ret = [x]
+        for s in plan:
+            lvl.fill_(s.level)
+            eps = self._eps(cond, img, lvl, guide, out=eps_buf)
+            noise = self._noise(img, s.k) if injected and s.sigma != 0.0 else None
+            fewstep_update_(img, eps, m_prev, s.c_recip, s.c_recipm1, s.flags, s.p, s.q, s.r, s.b1, s.store_m, s.sigma,
+                            seed=seed, step=s.k, seeds=seeds, noise=noise)
+            if continous:
+                ret.append(img.clone())
+        return ret if continous else [img.clone()]                  # (img may be the persistent graph-replay buffer)
+
     @torch.no_grad()
     def sample(self, batch_size=1, continous=False):
         raise NotImplementedError("unconditional sampling is not part of the UCDIR restoration path")
@@ -322,7 +450,10 @@ class ResiGaussianGuideDY(GaussianDiffusion):
     def super_resolution(self, x_in, continous=False):
         initx = self.predictor(x_in)
         self.pre_initx = initx
-        out = self.p_sample_loop(x_in, continous, kwargs={"guide": initx})
+        if self.sampler is not None:
+            out = self.fewstep_sample(x_in, continous=continous, kwargs={"guide": initx}, **self.sampler)
+        else:
+            out = self.p_sample_loop(x_in, continous, kwargs={"guide": initx})
         if continous and out.shape[0] != initx.shape[0]:
             reps = out.shape[0] // initx.shape[0]
             return out + initx.repeat(reps, 1, 1, 1)

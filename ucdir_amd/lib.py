@@ -44,6 +44,10 @@ _SIGS = {
     "ucdir_sampler_step_rng_batched": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_float, c_float, c_float, c_float, c_float,
                                                  c_void_p, ctypes.c_uint32, c_void_p]),
     "ucdir_fill_normal_batched": (c_int32, [c_void_p, c_int64, c_int64, c_void_p, ctypes.c_uint32, c_void_p]),
+    "ucdir_fewstep_update": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_int32, c_float, c_float,
+                                       c_float, c_float, c_int32, c_float, ctypes.c_uint64, ctypes.c_uint32, c_void_p]),
+    "ucdir_fewstep_update_batched": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_float, c_float, c_int32,
+                                               c_float, c_float, c_float, c_float, c_int32, c_float, c_void_p, ctypes.c_uint32, c_void_p]),
     "ucdir_gather_windows": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     "ucdir_sampler_step": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float,
                                      c_float, c_void_p]),

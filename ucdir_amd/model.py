@@ -17,7 +17,7 @@ from collections import OrderedDict
 import torch
 import torch.nn.functional as F
 
-from . import networks
+from . import diffusion, networks
 
 logger = logging.getLogger("base")
 
@@ -29,6 +29,8 @@ class DDPM:
         self.begin_step, self.begin_epoch = 0, 0
         self.netG = networks.define_G(opt).to(self.device)
         self.netG.set_loss(self.device)
+        # model.sampler (optional): DDIM / DPM-Solver++ in a few network calls instead of the T-step ancestral sampler
+        self.netG.sampler = diffusion.parse_sampler(opt["model"].get("sampler"))
         self.set_new_noise_schedule(opt["model"]["beta_schedule"]["train"], schedule_phase="train")
         self.load_network()
         self.setup_distributed()

@@ -342,6 +342,36 @@ def sampler_step_rng_(x_t, eps, seed, step, c_recip, c_recipm1, coef1, coef2, si
     return x_t
 
 
+FEWSTEP_CLIP, FEWSTEP_FACTORED = 1, 2      # flags of fewstep_update_
+
+
+def fewstep_update_(x, eps, m_prev, c_recip, c_recipm1, flags, p, q, r, b1, store_m, sigma, seed=0, step=0, seeds=None, noise=None):
+    """In-place update of the few-step samplers (csrc/fewstep.hip.h):
+    x0 = c_recip x - c_recipm1 eps (``FEWSTEP_FACTORED``: c_recip (x - c_recipm1 eps); ``FEWSTEP_CLIP``: clamped to [-1, 1]),
+    x <- p x0 + q x + r eps + b1 m_prev + sigma z, m_prev <- x0 when ``store_m``.  z is the noise of (seed, step, element) drawn in the kernel (``seeds``: per-sample streams as in ``sampler_step_rng_``),
+    or ``noise`` when given.  ``m_prev`` may be None when b1 == 0 and not ``store_m``."""
+    L = _lib.load()
+
+    def ok(t):
+        return t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and t.numel() == x.numel() and t.device == x.device
+    if not (x.is_cuda and x.is_contiguous() and x.dtype == torch.float32):
+        raise _lib.UcdirError("fewstep_update_ needs a contiguous fp32 CUDA tensor")
+    for name, t in (("eps", eps), ("m_prev", m_prev), ("noise", noise)):
+        if t is not None and not ok(t):
+            raise _lib.UcdirError(f"fewstep_update_: {name} must be a contiguous fp32 CUDA tensor shaped like x on its device")
+    coef = (float(c_recip), float(c_recipm1), int(flags), float(p), float(q), float(r), float(b1), int(bool(store_m)), float(sigma))
+    mp = _ptr(m_prev) if m_prev is not None else ctypes.c_void_p(0)
+    nz = _ptr(noise) if noise is not None else ctypes.c_void_p(0)
+    if seeds is not None:
+        _check_seeds(seeds, x, "fewstep_update_")
+        _lib.check(L.ucdir_fewstep_update_batched(_ptr(x), _ptr(eps), mp, nz, x.numel(), x.numel() // x.shape[0], *coef, _ptr(seeds),
+                                                  int(step), _stream_ptr(x.device)))
+        return x
+    _lib.check(L.ucdir_fewstep_update(_ptr(x), _ptr(eps), mp, nz, x.numel(), *coef, int(seed) & (2 ** 64 - 1), int(step),
+                                      _stream_ptr(x.device)))
+    return x
+
+
 def gather_windows(x, pad, win_dev, skip):
     """Window batch of the inter-step patch split in one launch (utils/util.py:113-137: reflect pad + one slice per window):
     x (B, C, H, W) fp32 CUDA, win_dev (nwin, 2) int32 CUDA = (h0, w0) in padded coordinates -> (nwin * B, C, skip, skip)."""
