@@ -40,7 +40,7 @@ extern "C" {
 
 /* 4: ucdir_gather_windows and ucdir_matrix_rate joined the interface (round 4); a binding built against version 3 must not load this library
  * silently (round-4 verdict).  Round 5 added no symbol: new kernels are dispatch changes behind the same entry points (A/B switches: the
- * environment variables of DESIGN.md and ucdir_debug_flag names "flash2", "persist_grid", ...). */
+ * environment variables of DESIGN.md and ucdir_debug_flag names "persist_grid", ...; "flash2": retired, measured result in EXPERIMENTS.md). */
 #define UCDIR_ABI_VERSION 5
 #define UCDIR_MAX_MULTS 8
 
@@ -165,9 +165,9 @@ int64_t ucdir_workspace_bytes(const ucdir_ctx* ctx);
  * -1 = environment default (UCDIR_NO_FLASH).  "splitk": 1 / 0 / -1 the same for split-K and unit splits of
  * under-filled grids (UCDIR_SPLITK).  "persist_grid": n > 0 launches the persistent kernels (akgm_ws) with n workgroups
  * instead of one per compute unit, 0 restores the default.  "wsb": 1 routes the AKGM tails of 8 / 16 channels per group
- * through akgm_ws32_kernel<8 | 16> instead of akgm_ws_kernel (A/B and tests), 0 / -1 (UCDIR_WSB) as above.  "convsk": 0 = 3x3 convs
+ * through akgm_ws32_kernel<8 | 16> instead of akgm_ws_kernel (tests), 0 / -1 = akgm_ws_kernel.  "convsk": 0 = 3x3 convs
  * on conv3x3_halo (the round-3 dispatch), 1 = conv_sk_kernel's persistent 8-wave stream-K kind forced, 2 = its one-shot 4-wave kind
- * forced (both regardless of the size thresholds: tests), -1 = environment default (UCDIR_NO_CONV_SK, UCDIR_CONV_SK_MODE).  Unknown
+ * forced (both regardless of the size thresholds: tests), -1 = environment default (UCDIR_NO_CONV_SK; the 4-wave kind).  Unknown
  * names are an error. */
 int32_t ucdir_debug_flag(const char* name, int32_t value);
 /* Host-side launch planning, callable without a device (tests): what = "ksplit" -> the K-split factor conv3x3_halo would use

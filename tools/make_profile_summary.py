@@ -33,7 +33,7 @@ def bench_name(k):
         return "akgm_ws64"
     if "akgm_ws32_kernel" in k:
         return "akgm_ws32"
-    if "flash_attn2_kernel" in k or "flash_attn_kernel" in k:
+    if "flash_attn2_kernel" in k:
         return "flash_attn<fp16>" if ", true>" in k else "flash_attn<bf16>"
     if "akgm_ws_kernel<16>" in k:
         return "akgm_ws<16>"

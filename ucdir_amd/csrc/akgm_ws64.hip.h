@@ -18,9 +18,11 @@
 //   * fold table Tc[9][256] of the current sample in LDS, accumulators start at it; statistics in 2^-20 fixed point per lane
 //     (partition-independent: a sample restored alone or in a batch gets bit-identical sums).
 #pragma once
+#include "asmops.hip.h"
 #include "akgm_ws32.hip.h"
 
-template <int NW> struct AkWs64 {
+struct AkWs64 {
+    static constexpr int NW = 8;                                  // waves per workgroup
     static constexpr int HPOS = 272;                              // halo positions per buffer: NPX + 2 (W + 2) + 2 <= 272
     static constexpr int HALO = HPOS * 128;                       // 34,816 = 17 x 2048: the swizzle survives the buffer switch
     static constexpr int HBYTES(int hpos) { return ((hpos + 15) / 16) * 2048; }
@@ -35,29 +37,24 @@ template <int NW> struct AkWs64 {
     static constexpr int lds(int hpos) { return 2 * HBYTES(hpos) + 2 * STAGE + 2 * ATT + TCS; }
 };
 
-// one LDS-DMA piece (1 KB: 64 lanes x 16 B) from a wave-uniform 64-bit base (SGPR pair) + a 32-bit per-lane byte offset to a wave-uniform
-// LDS address: no 64-bit VALU address arithmetic per piece, and hipcc does not count it (cdna guide 5.7): the kernel waits for its DMAs at the
-// tile top by hand, and no compiler-made LDS access is held back by a vmcnt(0) for a DMA the compiler knows nothing about
-__device__ __forceinline__ void w64_dma16(const void* sbase, unsigned voff, unsigned lds_dst) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(voff), "s"(sbase), "s"(lds_dst) : "memory", "m0");
-}
-
-// NPT = pixel tiles per tile (2 | 4: 64 | 128 positions); NW = waves per workgroup (8: half a group per workgroup, one workgroup per CU;
-// 4: a QUARTER group - 16 features x 8 sets = 128 rows - per workgroup, 80 KB of LDS: TWO independent workgroups per CU, so the two waves
-// of a SIMD belong to different workgroups and no barrier aligns them).  p.tiles_x = tiles per sample, p.tiles_y unused (1), p.tw = halo bytes
-template <int NPT, int NW, bool ASYM = false>
+// NPT = pixel tiles per tile (2 | 4: 64 | 128 positions).  NW = 8 waves per workgroup (half a group, one workgroup per CU) and ASYM = true are the
+// only kind built; they stay in the name so that profiles of earlier builds still match (the four-wave and symmetric kinds: profiles/EXPERIMENTS.md).
+// p.tiles_x = tiles per sample, p.tiles_y unused (1), p.tw = halo bytes.  The LDS-DMAs go through dma16_sbase (asmops.hip.h): hipcc does not count
+// them - the kernel waits for them at the tile top by hand, and no compiler-made LDS access is held back by a vmcnt(0) for them.
+template <int NPT, int NW, bool ASYM>
 __global__ __launch_bounds__(64 * NW, 2) void akgm_ws64_kernel(const AkgmHP p) {
-    using L = AkWs64<NW>;
+    static_assert(NW == AkWs64::NW && ASYM, "akgm_ws64_kernel: only the eight-wave kind with the chores on waves 0 - 3 is built");
+    using L = AkWs64;
     constexpr int NK = L::NK;
     constexpr int CPX = 512;                                       // channels per position
     constexpr int NPX = 32 * NPT;
     constexpr int FEAT = 4 * NW;                                   // output features of the workgroup
     constexpr int PP = 1024 / L::SEGB;                             // positions per residual / output piece of 1 KB
-    // ASYM (NW = 8): ALL the memory chores of a tile - the LDS-DMAs of the next tile, the stores of the previous one - are done by waves 0 - 3.
+    // ASYM: ALL the memory chores of a tile - the LDS-DMAs of the next tile, the stores of the previous one - are done by waves 0 - 3.
     // The matrix pipe of a SIMD goes to its OLDER wave whenever both have an MFMA ready (tools/micro/mfma_arb.hip): waves 0 - 3 run their K
     // loops unimpeded and then wait at the tile barrier, waves 4 - 7 only get the pipe while their partner is outside its K loops.  With the
     // chores on the older half, the younger half starts its first K loop right behind the barrier, under the partner's chores.
-    constexpr int NDW = ASYM ? 4 : NW;                             // waves that do the chores
+    constexpr int NDW = 4;                                         // waves that do the chores
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hh = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -78,7 +75,7 @@ __global__ __launch_bounds__(64 * NW, 2) void akgm_ws64_kernel(const AkgmHP p) {
 #define W64_STAMP() do {} while (0)
 #endif
     W64_STAMP();
-    constexpr int NROLE = 512 / FEAT;                              // 16 half groups | 32 quarter groups
+    constexpr int NROLE = 512 / FEAT;                              // 16 half groups
     const int nslots = (int)gridDim.x / NROLE;                     // tile ranges per role (the grid is a multiple of NROLE)
     const int role = lid / nslots, slot = lid - role * nslots;     // roles of one group sit on one XCD (XCD-contiguous lid): its halo lines stay in that L2
     const int Wp = p.Wp, Ptot = (p.H + 2) * Wp, Plast = p.H * Wp + p.W;     // positions of a sample; last valid position
@@ -103,10 +100,10 @@ __global__ __launch_bounds__(64 * NW, 2) void akgm_ws64_kernel(const AkgmHP p) {
     W64_STAMP();                                                   // weights resident
 
     // ---- tile-invariant lane constants ---------------------------------------------------------------------------------
-    // halo piece k (8 positions x 128 B): wave w stages pieces w, w + NW, ...; lane -> (halo position 8 k + lane / 8, physical chunk lane & 7);
+    // halo piece k (8 positions x 128 B): chore wave w stages pieces w, w + NDW, ...; lane -> (halo position 8 k + lane / 8, physical chunk lane & 7);
     // the logical chunk is physical ^ (position >> 1) & 7 = physical ^ (4 (k & 1) + lane / 16)
     const int npiece = (NPX + 2 * Wp + 2 + 7) >> 3;
-    constexpr int NHOP = (L::HPOS / 8 + NDW - 1) / NDW;            // halo DMA operations per (chore) wave at most (5 | 9)
+    constexpr int NHOP = (L::HPOS / 8 + NDW - 1) / NDW;            // halo DMA operations per chore wave at most (9)
     constexpr int NROP = NW / NDW;                                 // residual pieces per chore wave
     // B fragment of tap t, channel quarter 0, pixel tile 0, buffer 0: LDS byte address (quarter cq: ^ (cq << 5); pixel tile q: + q PSTEP)
     unsigned bt[9];
@@ -135,14 +132,14 @@ __global__ __launch_bounds__(64 * NW, 2) void akgm_ws64_kernel(const AkgmHP p) {
                 int sp = nti * NPX + 8 * k + (int)(ln >> 3);
                 sp = sp < Ptot ? sp : Ptot - 1;                     // (the last tile's halo may run past the sample: clamped, feeds dropped positions only)
                 const unsigned off = (unsigned)sp * (CPX * 2) + (unsigned)(gch0 + (((ln & 7) ^ (4 * (k & 1) + (ln >> 4))) << 3)) * 2;
-                w64_dma16(p.h + (long long)nb * p.h_bstride, off, (unsigned)__builtin_amdgcn_readfirstlane(buf * HB + k * 1024));
+                dma16_sbase(p.h + (long long)nb * p.h_bstride, off, (unsigned)__builtin_amdgcn_readfirstlane(buf * HB + k * 1024));
             }
         } else if constexpr (op == NHOP) {
             if (wave < NPT) {
                 int P = Wp + 1 + nti * NPX + 32 * wave + (int)(ln >> 1); P = P < Ptot ? P : Ptot - 1;
                 int y = fdiv_small(P, inv_wp), x = P - y * Wp;
                 y = y < 1 ? 1 : (y > p.H ? p.H : y); x = x < 1 ? 1 : (x > p.W ? p.W : x);
-                w64_dma16(p.G + (long long)nb * p.g_bstride, (unsigned)((((y - 1) * p.W + (x - 1)) * 8 + (int)(ln & 1) * 4) * 4),
+                dma16_sbase(p.G + (long long)nb * p.g_bstride, (unsigned)((((y - 1) * p.W + (x - 1)) * 8 + (int)(ln & 1) * 4) * 4),
                           (unsigned)__builtin_amdgcn_readfirstlane(OFF_ATT + buf * L::ATT + wave * 1024));
             }
         } else {
@@ -152,7 +149,7 @@ __global__ __launch_bounds__(64 * NW, 2) void akgm_ws64_kernel(const AkgmHP p) {
                 const unsigned pos = PP * piece + ln / L::CPS;
                 int P = Wp + 1 + nti * NPX + (int)pos; P = P < Ptot ? P : Ptot - 1;
                 const unsigned off = (unsigned)P * (CPX * 2) + (unsigned)(chan0 + (((ln & (L::CPS - 1)) ^ ((pos >> 2) & (L::CPS - 1))) << 3)) * 2;
-                w64_dma16(p.res + (long long)nb * p.res_bstride, off, (unsigned)__builtin_amdgcn_readfirstlane(OFF_STAGE + buf * L::STAGE + piece * 1024));
+                dma16_sbase(p.res + (long long)nb * p.res_bstride, off, (unsigned)__builtin_amdgcn_readfirstlane(OFF_STAGE + buf * L::STAGE + piece * 1024));
             }
         }
     };
@@ -199,23 +196,19 @@ __global__ __launch_bounds__(64 * NW, 2) void akgm_ws64_kernel(const AkgmHP p) {
             }
             S1 = 0; S2 = 0;
             b_cur = b;
-            // fold table slice [9][32 NW] of this sample: piece pc = classes (NW == 8: pc, 64 lanes x 16 B; NW == 4: 2 pc and 2 pc + 1, 32 lanes each)
-            constexpr int NTP = (NW == 8) ? 9 : 5;
+            // fold table slice [9][32 NW] of this sample: piece pc = class pc, 64 lanes x 16 B
             float mean_b = 0.f;
             if (p.own_tc) stat_mean_rstd_wave(p.stats, b, p.inv_count, lane, mean_b, rstd);
             else rstd = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, p.ms[2 * b + 1])));
             const float inv_b = 1.0f / rstd;
 #pragma unroll
-            for (int i = 0; i < (NTP + NW - 1) / NW; ++i) {
+            for (int i = 0; i < (9 + NW - 1) / NW; ++i) {
                 const int pc = i * NW + wave;
-                if (pc < NTP) {
-                    const int cl = (NW == 8) ? pc : 2 * pc + (lane >> 5), e4 = (NW == 8) ? lane : (lane & 31);
-                    if (cl < 9) {
-                        const long long rel = (long long)cl * (8 * CPX) + 8 * chan0 + e4 * 4;
-                        if (p.own_tc) akgm_tc_piece(p, rel, smem + OFF_TCS + pc * 1024 + lane * 16, inv_b, mean_b);
-                        else __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)(p.Tc + (long long)b * 9 * (8 * CPX) + rel),
-                                                              (LDS_AS void*)(smem + OFF_TCS + pc * 1024), 16, 0, 0);
-                    }
+                if (pc < 9) {
+                    const long long rel = (long long)pc * (8 * CPX) + 8 * chan0 + lane * 4;
+                    if (p.own_tc) akgm_tc_piece(p, rel, smem + OFF_TCS + pc * 1024 + lane * 16, inv_b, mean_b);
+                    else __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)(p.Tc + (long long)b * 9 * (8 * CPX) + rel),
+                                                          (LDS_AS void*)(smem + OFF_TCS + pc * 1024), 16, 0, 0);
                 }
             }
 #pragma unroll

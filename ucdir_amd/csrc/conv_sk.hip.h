@@ -33,6 +33,7 @@
 // alternative (ucdir_debug_flag("convsk", 1)).
 // Reference: model/ucdir.py:110 (block conv1), :57 (Upsample conv), SURVEY.md Appendix A.
 #pragma once
+#include "asmops.hip.h"
 #include "conv_halo.hip.h"
 #include "akgm_ws.hip.h"
 
@@ -101,13 +102,6 @@ struct CvSk {
 #else
 #define SK_STAMP() do {} while (0)
 #endif
-
-// one LDS-DMA piece with a wave-uniform (SGPR) base and a 32-bit per-lane byte offset: no 64-bit VALU address arithmetic per piece (the
-// builtin always takes a per-lane 64-bit pointer).  hipcc does not count it (cdna guide 5.7): the kernel's waits are counted by hand anyway;
-// M0 (the LDS destination) is written inside the statement.
-__device__ __forceinline__ void sk_dma16(const void* sbase, unsigned voff, unsigned lds_dst) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(voff), "s"(sbase), "s"(lds_dst) : "memory", "m0");
-}
 
 template <int N>
 __device__ __forceinline__ void sk_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
@@ -547,12 +541,12 @@ __device__ __forceinline__ void conv_sk_body(const ConvSkP& p, unsigned char* sm
     const unsigned lane16 = (unsigned)lane * 16u;
     int seg_cb = 0;
     auto issue_halo = [&](int j, int buf) {                          // piece j of the chunk of halo_chunk() into halo buffer buf
-        sk_dma16(hsrc, hq[j], (unsigned)(L::OFF_H + piece_of(j) * 1024 + buf * HB));
+        dma16_sbase(hsrc, hq[j], (unsigned)(L::OFF_H + piece_of(j) * 1024 + buf * HB));
     };
     auto issue_stage = [&](int k, int slot) {                        // stage k of the segment's (parity, row tile); past its end: whatever follows
 #pragma unroll                                                       // in the image (the image is padded by four stages) into a slot nobody reads any more
         for (int j = 0; j < PWN; ++j)
-            sk_dma16(a_seg + (long long)k * L::STAGE + j * 1024, lane16, (unsigned)(L::OFF_W + slot * L::STAGE + (wave * PWN + j) * 1024));
+            dma16_sbase(a_seg + (long long)k * L::STAGE + j * 1024, lane16, (unsigned)(L::OFF_W + slot * L::STAGE + (wave * PWN + j) * 1024));
     };
     // one-shot kind: the fold tables of the segment's row tile (bias | Tb[9] | Tg[9], 128 floats each: 19 half pieces) take the place of the
     // halo pieces that the last chunk would request for a chunk that does not exist - same instruction count, idle halo buffer
@@ -732,7 +726,7 @@ __device__ __forceinline__ void conv_sk_body(const ConvSkP& p, unsigned char* sm
                                 else issue_halo(j, bnext ? 1 : 0);
                             } else {
                                 constexpr int j = q - nh;
-                                sk_dma16(a_seg + (long long)(cb * NTAPS + h + 4) * L::STAGE + j * 1024, lane16, (unsigned)(L::OFF_W + (h & 3) * L::STAGE + (wave * PWN + j) * 1024));
+                                dma16_sbase(a_seg + (long long)(cb * NTAPS + h + 4) * L::STAGE + j * 1024, lane16, (unsigned)(L::OFF_W + (h & 3) * L::STAGE + (wave * PWN + j) * 1024));
                             }
                         }
                     });

@@ -25,7 +25,6 @@
 #include "conv_ws.hip.h"
 #include "conv_sk.hip.h"
 #include "conv_ws128.hip.h"
-#include "flash_attn.hip.h"
 #include "flash_attn2.hip.h"
 #include "qkv_ws.hip.h"
 #include "common.h"
@@ -228,8 +227,6 @@ static void ensure_kernel_attrs() {
     set_lds_attr(akgm_pre_kernel<8>, AkPre<8>::LDS);
     set_lds_attr(akgm_ws_kernel<8>, AkWs::LDS); set_lds_attr(akgm_ws_kernel<16>, AkWs::LDS);
     set_lds_attr(akgm_ws32_kernel<32>, AkWs32::LDS); set_lds_attr(akgm_ws32_kernel<16>, AkWs32::LDS); set_lds_attr(akgm_ws32_kernel<8>, AkWs32::LDS);
-    set_lds_attr(akgm_ws64_kernel<2, 4>, 160 * 1024); set_lds_attr(akgm_ws64_kernel<4, 4>, 160 * 1024);
-    set_lds_attr(akgm_ws64_kernel<2, 8>, 160 * 1024); set_lds_attr(akgm_ws64_kernel<4, 8>, 160 * 1024);
     set_lds_attr(akgm_ws64_kernel<2, 8, true>, 160 * 1024); set_lds_attr(akgm_ws64_kernel<4, 8, true>, 160 * 1024);
     set_lds_attr(qkv_ws_kernel<256>, QkvWs::LDS); set_lds_attr(qkv_ws_kernel<512>, QkvWs::LDS);
     set_lds_attr(conv_ws_kernel, CvWs::LDS);
@@ -239,10 +236,6 @@ static void ensure_kernel_attrs() {
     set_lds_attr(conv_sk_kernel<1, 4, 9>, 80 * 1024, true); set_lds_attr(conv_sk_kernel<1, 4, 4>, 80 * 1024, true);
 
     set_lds_attr(final_conv_kernel, 160 * 1024);
-    set_lds_attr(flash_attn_kernel<1, false>, fa_lds_bytes(128)); set_lds_attr(flash_attn_kernel<1, true>, fa_lds_bytes(128));
-    set_lds_attr(flash_attn_kernel<2, false>, fa_lds_bytes(256)); set_lds_attr(flash_attn_kernel<2, true>, fa_lds_bytes(256));
-    set_lds_attr(flash_attn_kernel<3, false>, fa_lds_bytes(384)); set_lds_attr(flash_attn_kernel<3, true>, fa_lds_bytes(384));
-    set_lds_attr(flash_attn_kernel<4, false>, fa_lds_bytes(512)); set_lds_attr(flash_attn_kernel<4, true>, fa_lds_bytes(512));
     set_lds_attr(flash_attn2_kernel<1, false>, fa_lds_bytes(128), true); set_lds_attr(flash_attn2_kernel<1, true>, fa_lds_bytes(128), true);
     set_lds_attr(flash_attn2_kernel<2, false>, fa_lds_bytes(256), true); set_lds_attr(flash_attn2_kernel<2, true>, fa_lds_bytes(256), true);
     set_lds_attr(flash_attn2_kernel<3, false>, fa_lds_bytes(384), true); set_lds_attr(flash_attn2_kernel<3, true>, fa_lds_bytes(384), true);
@@ -389,7 +382,7 @@ static void launch_halo(const GemmP& p, hipStream_t st) {
 static std::atomic<bool> g_use_halo{true};
 
 // compute units of the current device (persistent kernels launch one workgroup per CU)
-static std::atomic<int> g_wsb{-1};             // -1: environment (UCDIR_WSB), 0 / 1: ucdir_debug_flag("wsb", v): block AKGM kernel also at 8 / 16 channels per group
+static std::atomic<int> g_wsb{-1};             // ucdir_debug_flag("wsb", 1): block AKGM kernel also at 8 / 16 channels per group (tests); -1 / 0: off
 static std::atomic<int> g_persist_grid{0};     // > 0: ucdir_debug_flag("persist_grid", n) forces the grid of the persistent kernels (tests: many tiles per workgroup on small inputs)
 static int num_cus() {
     if (g_persist_grid > 0) return g_persist_grid;
@@ -474,18 +467,16 @@ static bool try_conv_sk_mw(const ConvW& w, const Act& x0, const Act* x1, Act& y,
     const int NPX = L::NPX;
     // vertical strips: the fewest whose halo (NPX + 2 (Ws + 2) + 2 positions of 64 bytes, two buffers) fits the workgroup's LDS and the
     // kernel's fixed number of halo pieces
-    // shared borders (conv_sk.hip.h, ConvSkP): H + 1 rows per (sample, strip), W + 1 columns when the image is one strip; UCDIR_SK_CLASSIC=1: the
-    // zero-bordered [H + 2][Ws + 2] space of rounds 4 - 5 (A/B)
-    static const bool sk_shared = !getenv("UCDIR_SK_CLASSIC");
+    // shared borders (conv_sk.hip.h, ConvSkP): H + 1 rows per (sample, strip), W + 1 columns when the image is one strip
     int ns = 1, Ws = W, nhp = 0, Wpe = W + 2;
     for (;; ++ns) {
         Ws = (W + ns - 1) / ns;
-        Wpe = (sk_shared && ns == 1) ? Ws + 1 : Ws + 2;
+        Wpe = ns == 1 ? Ws + 1 : Ws + 2;
         nhp = (NPX + 2 * Wpe + 2 + 15) / 16;
         if (nhp <= L::NHP_MAX && L::lds_bytes(nhp) <= L::LDS_MAX) break;
         if (Ws <= 8) return false;
     }
-    const int HpWpe = (sk_shared ? H + 1 : Hp) * Wpe;
+    const int HpWpe = (H + 1) * Wpe;
     const long long npos = (long long)B * ns * HpWpe;
     if ((long long)B * Hp * Wp * (long long)(cin > y.C ? cin : y.C) * (upph ? 4 : 1) >= (1LL << 31) || npos >= (1LL << 30)) return false;   // 32-bit offsets in the kernel
     ConvSkP p; std::memset(&p, 0, sizeof(p));
@@ -519,18 +510,16 @@ static bool try_conv_sk_mw(const ConvW& w, const Act& x0, const Act* x1, Act& y,
         p.ndp = (p.units / G) * G;
     } else {                                                         // one workgroup per unit, two resident per CU
         G = p.units; p.ndp = p.units;
-        static const int persist = getenv("UCDIR_SK_PERSIST") ? atoi(getenv("UCDIR_SK_PERSIST")) : 0;   // experiment: ranges of whole units on 2 x CUs workgroups from `persist` units per workgroup on
-        if (persist > 0 && G >= persist * 2 * num_cus()) G = 2 * num_cus();
         if (g_persist_grid > 0) { G = g_persist_grid < p.units ? (int)g_persist_grid : p.units; if (2 * G > 2 * SK_MAX_GRID) G = SK_MAX_GRID; p.ndp = (p.units / G) * G; }   // (tests: ranges and a stream-K remainder)
         // measured per layer at B = 16 (tools/conv_layers.py): ahead of conv3x3_halo<128> from 4 chunks of K on (Upsample classes: 8 - a class
         // has only four sub-steps per halo chunk) once every CU has a workgroup
         // few long units (the 18^2 level at B = 16: 100 units of 144 - 288 sub-steps for 256 CUs): every unit's K range cut in two, one
         // workgroup each, the finish kernel sums the halves in part order.  Per launch incl. the finish pass, tools/conv_layers.py:
         // 1024 -> 512 101 -> 83 us, 512 -> 512 62 -> 59 us (three and four parts: 97 / 87 us - every part pays its own prologue and
-        // partial-tile store).  UCDIR_SK_KSPLIT=<n> (0 / 1: off) for A/B.  Not below 64 units: B = 1 keeps its split-K path.
-        static const int ksplit_env = getenv("UCDIR_SK_KSPLIT") ? atoi(getenv("UCDIR_SK_KSPLIT")) : 2;
-        if (ksplit_env > 1 && g_persist_grid <= 0 && p.units >= 64 && p.units * ksplit_env <= 2 * num_cus() && p.nchunks >= 8 * ksplit_env && !upph) {
-            G = p.units * ksplit_env; p.ndp = 0; ksplit_on = true;
+        // partial-tile store).  Not below 64 units: B = 1 keeps its split-K path.
+        constexpr int KSPLIT = 2;
+        if (g_persist_grid <= 0 && p.units >= 64 && p.units * KSPLIT <= 2 * num_cus() && p.nchunks >= 8 * KSPLIT && !upph) {
+            G = p.units * KSPLIT; p.ndp = 0; ksplit_on = true;
         } else if (mode < 0 && (p.units < num_cus() || p.nchunks < (upph ? 8 : 4))) return false;
     }
     // A stream-K remainder with fewer chunks than workgroups would leave workgroups WITHOUT a chunk range: they write no partial slot, and the
@@ -628,15 +617,14 @@ static bool try_conv_sk_mw(const ConvW& w, const Act& x0, const Act* x1, Act& y,
     HIPC(hipGetLastError());
     return true;
 }
-// g_convsk: -1 environment (UCDIR_NO_CONV_SK, UCDIR_CONV_SK_MODE) + work thresholds; 0 off; 1: persistent stream-K workgroups of 8 waves forced;
-// 2: one-shot 4-wave workgroups (two per CU) forced
+// g_convsk: -1 environment (UCDIR_NO_CONV_SK) + work thresholds, one-shot 4-wave workgroups; 0 off; 1: persistent stream-K workgroups of 8 waves
+// forced; 2: one-shot 4-wave workgroups (two per CU) forced
 static bool try_conv_sk(const ConvW& w, const Act& x0, const Act* x1, Act& y, bool upph, int act, const Act* res, bool want_stats, hipStream_t st, bool* did_res, Act* res_out, const ConvW* wres) {
     static const bool env_on = !getenv("UCDIR_NO_CONV_SK");
-    static const int env_kind = getenv("UCDIR_CONV_SK_MODE") ? atoi(getenv("UCDIR_CONV_SK_MODE")) : 2;
     const int mode = g_convsk.load();
     if (mode == 0 || (mode < 0 && !env_on)) return false;
     if (x0.C % 32 || (x1 && x1->C % 32) || y.C % 8) return false;
-    const int kind = mode > 0 ? mode : env_kind;
+    const int kind = mode > 0 ? mode : 2;
     const int fm = mode > 0 ? 1 : -1;
     if (kind == 2) return try_conv_sk_mw<1, 4>(w, x0, x1, y, upph, act, res, want_stats, st, fm, did_res, res_out, wres);
     if (w.cout % 256 == 0) return try_conv_sk_mw<2, 8>(w, x0, x1, y, upph, act, res, want_stats, st, fm, did_res, nullptr, nullptr);
@@ -846,8 +834,8 @@ static void run_akgm_halo(const AkgmW& w, const Act& h1, const float* G, const f
     AkgmHP p;
     // akgm_ws_kernel<8 | 16> walk their tile ranges BACKWARDS: the producer of h1 (conv_ws / conv_sk) wrote its ranges ascending, so the lines it wrote
     // last - still in the XCD's L2 and the Infinity Cache - are met first (tools/micro/mall_order.hip: a streaming consumer of a 172 MB tensor runs 6 - 13 %
-    // faster descending; in the network akgm_ws<8> 2.58 -> 2.53 ms per three forwards, akgm_ws<16> 1.76 -> 1.74).  UCDIR_AKGM_REV=0: ascending (A/B)
-    { static const int rev = getenv("UCDIR_AKGM_REV") ? atoi(getenv("UCDIR_AKGM_REV")) : 1; p.reverse = rev; }
+    // faster descending; in the network akgm_ws<8> 2.58 -> 2.53 ms per three forwards, akgm_ws<16> 1.76 -> 1.74)
+    p.reverse = 1;
     p.A = pre ? w.Apre : w.A; p.Kpad = w.Kpad; p.h = h1.p; p.h_bstride = h1.bstride();
     p.C = w.C; p.cg = w.cg; p.H = y.H; p.W = y.W; p.Wp = y.W + 2;
     choose_tile(y.H, y.W, p.th, p.tw);
@@ -882,28 +870,24 @@ static void run_akgm_halo(const AkgmW& w, const Act& h1, const float* G, const f
     static const bool use_ws32 = !getenv("UCDIR_NO_WS32");
     int th32 = 0;
     for (int cand : {32, 24, 16, 8}) if (y.H % cand == 0) { th32 = cand; break; }
-    // (UCDIR_WSB=1: the block kernel also at 8 / 16 channels per group instead of akgm_ws_kernel - A/B switch)
-    static const bool wsb_env = getenv("UCDIR_WSB") != nullptr;
-    const bool wsb_all = g_wsb < 0 ? wsb_env : g_wsb != 0;
+    // (ucdir_debug_flag("wsb", 1): the block kernel also at 8 / 16 channels per group instead of akgm_ws_kernel - tests)
+    const bool wsb_all = g_wsb > 0;
     const int nb32 = w.C / 32;
     const bool ws32 = use_ws && use_ws32 && w.Aws32 != nullptr && (w.cg == 32 || (wsb_all && (w.cg == 16 || w.cg == 8))) && w.C == 8 * w.cg && th32 > 0 && y.W % 8 == 0 &&
                       (g_persist_grid > 0 || (long long)y.B * (y.H / th32) * (y.W / 8) * nb32 >= 4LL * num_cus());
     if (ws32) { p.A = w.Aws32; p.th = th32; p.tw = 8; p.tiles_x = y.W / 8; p.tiles_y = y.H / th32; }
     // 64 channels per group (C = 512: the 36^2 / 18^2 levels), akgm_ws64.hip.h: half a group per workgroup of eight waves, one per CU, the tile's
-    // memory chores on waves 0 - 3 (UCDIR_WS64_SYM=1: split over all eight; UCDIR_WS64_NW=4: a quarter group per workgroup of four waves, two
-    // independent workgroups per CU); linear tiles of 64 | 128 positions of the zero-bordered plane; roles x (resident workgroups / roles) tile
+    // memory chores on waves 0 - 3; linear tiles of 64 | 128 positions of the zero-bordered plane; roles x (resident workgroups / roles) tile
     // ranges.  From two tiles per range on (B = 1 keeps the one-shot kernel and its unit split); UCDIR_NO_WS64 falls back to akgm_halo_stage_kernel
     static const bool use_ws64 = !getenv("UCDIR_NO_WS64");
-    static const int ws64_nw = (getenv("UCDIR_WS64_NW") && atoi(getenv("UCDIR_WS64_NW")) == 4) ? 4 : 8;
-    static const bool ws64_asym = getenv("UCDIR_WS64_SYM") == nullptr;       // NW = 8: the tile's memory chores on waves 0 - 3 only
     int npt64 = 0, tps64 = 0, grid64 = 0, lds64 = 0;
     if (use_ws && use_ws64 && w.Aws64 != nullptr && w.cg == 64 && w.C == 512 && y.H >= 2 && (y.H + 2) * (y.W + 2) < 32768) {
-        const int nrole = 128 / ws64_nw, resident = (ws64_nw == 4 ? 2 : 1) * num_cus();
-        grid64 = resident / nrole * nrole; if (grid64 < nrole) grid64 = nrole;
+        const int nrole = 128 / AkWs64::NW;
+        grid64 = num_cus() / nrole * nrole; if (grid64 < nrole) grid64 = nrole;
         const int span = (y.H - 1) * (y.W + 2) + y.W, nslots = grid64 / nrole;
         for (int cand : {4, 2}) {
             const int hpos = 32 * cand + 2 * (y.W + 2) + 2;
-            if (hpos > AkWs64<4>::HPOS) continue;
+            if (hpos > AkWs64::HPOS) continue;
             const int tps = (span + 32 * cand - 1) / (32 * cand);
             // engage from four 128-position tiles per range on; with 64-position tiles when a range has at least 1.5 x the positions of one
             // tile's halo (measured against akgm_halo_stage, tools/bench_op.py akgm: B = 3 at 36^2 34 vs 39 us, B = 8 at 18^2 24.5 vs 26.1; below that
@@ -911,11 +895,8 @@ static void run_akgm_halo(const AkgmW& w, const Act& h1, const float* G, const f
             const bool enough = cand == 4 ? (long long)y.B * tps >= 4LL * nslots : 2LL * y.B * span >= 3LL * nslots * hpos;
             if (g_persist_grid > 0 || enough) {
                 npt64 = cand; tps64 = tps;
-                lds64 = ws64_nw == 4 ? AkWs64<4>::lds(hpos) : AkWs64<8>::lds(hpos);
-                p.tw = AkWs64<4>::HBYTES(hpos);
-                // (round-5 advice) four-wave workgroups are only co-resident in pairs while two of them fit the CU's 160 KB: wide planes
-                // (hpos ~272: 90.6 KB) leave one per CU - the grid then covers one resident workgroup per CU, not two half-rounds
-                if (ws64_nw == 4 && 2 * lds64 > 160 * 1024 && g_persist_grid <= 0) { grid64 = num_cus() / nrole * nrole; if (grid64 < nrole) grid64 = nrole; }
+                lds64 = AkWs64::lds(hpos);
+                p.tw = AkWs64::HBYTES(hpos);
                 break;
             }
         }
@@ -931,16 +912,8 @@ static void run_akgm_halo(const AkgmW& w, const Act& h1, const float* G, const f
         hipLaunchKernelGGL(akgm_tc_kernel, dim3(9 * ((8 * w.C + 1023) / 1024), y.B), dim3(256), 0, st, h1.stats, inv_cnt, w.bias, w.Tb, w.Tg, 8 * w.C, tcbuf, msbuf);
     auto launch = [&]() {
         if (ws64) {
-            if (ws64_nw == 4) {
-                if (npt64 == 4) hipLaunchKernelGGL((akgm_ws64_kernel<4, 4>), dim3(grid64), dim3(256), lds64, st, p);
-                else hipLaunchKernelGGL((akgm_ws64_kernel<2, 4>), dim3(grid64), dim3(256), lds64, st, p);
-            } else if (ws64_asym) {
-                if (npt64 == 4) hipLaunchKernelGGL((akgm_ws64_kernel<4, 8, true>), dim3(grid64), dim3(512), lds64, st, p);
-                else hipLaunchKernelGGL((akgm_ws64_kernel<2, 8, true>), dim3(grid64), dim3(512), lds64, st, p);
-            } else {
-                if (npt64 == 4) hipLaunchKernelGGL((akgm_ws64_kernel<4, 8>), dim3(grid64), dim3(512), lds64, st, p);
-                else hipLaunchKernelGGL((akgm_ws64_kernel<2, 8>), dim3(grid64), dim3(512), lds64, st, p);
-            }
+            if (npt64 == 4) hipLaunchKernelGGL((akgm_ws64_kernel<4, 8, true>), dim3(grid64), dim3(512), lds64, st, p);
+            else hipLaunchKernelGGL((akgm_ws64_kernel<2, 8, true>), dim3(grid64), dim3(512), lds64, st, p);
         } else if (ws32) {
             const int ntiles = y.B * p.tiles_x * p.tiles_y;
             int ncu = num_cus() / nb32 * nb32; if (ncu < nb32) ncu = nb32;
@@ -1033,7 +1006,6 @@ struct AttnBufs {
 };
 
 static std::atomic<int> g_flash{-1};          // -1: environment (UCDIR_NO_FLASH), 0 / 1: ucdir_debug_flag("flash", v)
-static std::atomic<int> g_flash2{-1};         // -1: environment (UCDIR_FLASH1), 0: flash_attn_kernel, 1: flash_attn2_kernel (ucdir_debug_flag("flash2", v))
 static bool flash_ok(int C) {
     static const bool env_on = !getenv("UCDIR_NO_FLASH");
     const bool on = g_flash < 0 ? env_on : g_flash != 0;
@@ -1128,7 +1100,7 @@ static void run_attention(const ConvW& wqkv, const ConvW& wout, const Act& x, Ac
                        a.qkv, N, 3 * C, 2 * C, C, Npad, a.Vt);
     }
     if (a.flash) {
-        // 3. one kernel: QK^T -> online softmax -> P V' + bias + x, GroupNorm statistics of y (flash_attn.hip.h)
+        // 3. one kernel: QK^T -> online softmax -> P V' + bias + x, GroupNorm statistics of y (flash_attn2.hip.h)
         FlashP f;
         f.qkv = a.qkv; f.qkv_bstride = (long long)N * 3 * C; f.ld = 3 * C;
         f.vt = a.Vt; f.vt_bstride = (long long)C * Npad; f.Npad = Npad;
@@ -1146,35 +1118,19 @@ static void run_attention(const ConvW& wqkv, const ConvW& wout, const Act& x, Ac
         f.dbg = fdbg;
 #endif
         const dim3 grid((unsigned)(B * f.nq));
-        // flash_attn2_kernel (round 5, the default): flash_attn_kernel's structure (128 queries per workgroup, 64-key tiles, all eight waves in one
-        // phase, two barriers per tile) with every fragment read of the S and PV phases as inline asm with counted lgkmcnt; same LDS layout and size.
-        // UCDIR_FLASH1=1 / ucdir_debug_flag("flash2", 0) selects the round-2 kernel (compiler-scheduled reads)
-        static const bool flash1_env = getenv("UCDIR_FLASH1") != nullptr;
-        const bool flash2 = g_flash2 < 0 ? !flash1_env : g_flash2 != 0;
+        // flash_attn2_kernel: 128 queries per workgroup, 64-key tiles, all eight waves in one phase, two barriers per tile, every fragment read of
+        // the S and PV phases as inline asm with counted lgkmcnt
         const size_t lds = fa_lds_bytes(C);
         auto launch = [&]() {
-            if (flash2) {
-                switch (C / 128 * 2 + (a.half ? 1 : 0)) {
-                    case 2: hipLaunchKernelGGL((flash_attn2_kernel<1, false>), grid, dim3(FA_THREADS), lds, st, f); break;
-                    case 3: hipLaunchKernelGGL((flash_attn2_kernel<1, true>), grid, dim3(FA_THREADS), lds, st, f); break;
-                    case 4: hipLaunchKernelGGL((flash_attn2_kernel<2, false>), grid, dim3(FA_THREADS), lds, st, f); break;
-                    case 5: hipLaunchKernelGGL((flash_attn2_kernel<2, true>), grid, dim3(FA_THREADS), lds, st, f); break;
-                    case 6: hipLaunchKernelGGL((flash_attn2_kernel<3, false>), grid, dim3(FA_THREADS), lds, st, f); break;
-                    case 7: hipLaunchKernelGGL((flash_attn2_kernel<3, true>), grid, dim3(FA_THREADS), lds, st, f); break;
-                    case 8: hipLaunchKernelGGL((flash_attn2_kernel<4, false>), grid, dim3(FA_THREADS), lds, st, f); break;
-                    default: hipLaunchKernelGGL((flash_attn2_kernel<4, true>), grid, dim3(FA_THREADS), lds, st, f); break;
-                }
-                return;
-            }
             switch (C / 128 * 2 + (a.half ? 1 : 0)) {
-                case 2: hipLaunchKernelGGL((flash_attn_kernel<1, false>), grid, dim3(FA_THREADS), lds, st, f); break;
-                case 3: hipLaunchKernelGGL((flash_attn_kernel<1, true>), grid, dim3(FA_THREADS), lds, st, f); break;
-                case 4: hipLaunchKernelGGL((flash_attn_kernel<2, false>), grid, dim3(FA_THREADS), lds, st, f); break;
-                case 5: hipLaunchKernelGGL((flash_attn_kernel<2, true>), grid, dim3(FA_THREADS), lds, st, f); break;
-                case 6: hipLaunchKernelGGL((flash_attn_kernel<3, false>), grid, dim3(FA_THREADS), lds, st, f); break;
-                case 7: hipLaunchKernelGGL((flash_attn_kernel<3, true>), grid, dim3(FA_THREADS), lds, st, f); break;
-                case 8: hipLaunchKernelGGL((flash_attn_kernel<4, false>), grid, dim3(FA_THREADS), lds, st, f); break;
-                default: hipLaunchKernelGGL((flash_attn_kernel<4, true>), grid, dim3(FA_THREADS), lds, st, f); break;
+                case 2: hipLaunchKernelGGL((flash_attn2_kernel<1, false>), grid, dim3(FA_THREADS), lds, st, f); break;
+                case 3: hipLaunchKernelGGL((flash_attn2_kernel<1, true>), grid, dim3(FA_THREADS), lds, st, f); break;
+                case 4: hipLaunchKernelGGL((flash_attn2_kernel<2, false>), grid, dim3(FA_THREADS), lds, st, f); break;
+                case 5: hipLaunchKernelGGL((flash_attn2_kernel<2, true>), grid, dim3(FA_THREADS), lds, st, f); break;
+                case 6: hipLaunchKernelGGL((flash_attn2_kernel<3, false>), grid, dim3(FA_THREADS), lds, st, f); break;
+                case 7: hipLaunchKernelGGL((flash_attn2_kernel<3, true>), grid, dim3(FA_THREADS), lds, st, f); break;
+                case 8: hipLaunchKernelGGL((flash_attn2_kernel<4, false>), grid, dim3(FA_THREADS), lds, st, f); break;
+                default: hipLaunchKernelGGL((flash_attn2_kernel<4, true>), grid, dim3(FA_THREADS), lds, st, f); break;
             }
         };
         if (g_prof.on) {
@@ -1942,8 +1898,7 @@ int32_t ucdir_debug_read(ucdir_ctx* ctx, const char* layer, const char* what, fl
 int32_t ucdir_debug_flag(const char* name, int32_t value) {
     API_BEGIN
     require(name != nullptr, "null argument");
-    if (!strcmp(name, "flash2")) g_flash2 = value;       // flash kernel: 1 phase-shifted halves (flash_attn2), 0 round-2 kernel, -1 environment
-    else if (!strcmp(name, "flash")) g_flash = value;            // attention: 1 flash kernel, 0 materialised scores, -1 environment
+    if (!strcmp(name, "flash")) g_flash = value;            // attention: 1 flash kernel, 0 materialised scores, -1 environment
     else if (!strcmp(name, "splitk")) g_splitk = value;     // split-K / unit split for under-filled grids: 1 on, 0 off, -1 environment
     else if (!strcmp(name, "wsb")) g_wsb = value;
     else if (!strcmp(name, "skmix")) g_skmix = value;         // conv_sk_kernel<1, 4, 9> with wide + short units: 1 forced at any size, 0 off, -1 environment + occupancy rule

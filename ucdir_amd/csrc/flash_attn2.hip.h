@@ -1,7 +1,35 @@
-// Flash attention, second version (round 5; model/ucdir.py:165-182): flash_attn.hip.h's structure, operands, LDS layout and epilogue - 128 queries per
-// workgroup, 64-key tiles, S phase / softmax / PV phase with two barriers per tile - with every fragment read of the two MFMA phases as INLINE
-// ASM with COUNTED lgkmcnt waits.  hipcc's own LDS bookkeeping drains the queue (lgkmcnt(0)) every few MFMAs, so both phases of
-// flash_attn_kernel are LDS-LATENCY bound: ~50 cycles per 16-cycle MFMA in the S phase, ~150 per 32-cycle MFMA in the PV phase (s_memtime
+// Single-head self-attention with a 512-wide (C = 128 .. 512) head as ONE kernel (gfx950):
+//   y[i][:] = sum_j softmax_j(q_i . k_j / sqrt(C)) v'_j + bias + x_i          (model/ucdir.py:165-182)
+// q, k come from the compact token tensor qkv [B][N][3C] (q at 0, k at C), v' = W_o W_v GN(x) arrives transposed,
+// V't [B][C][Npad] (fold_out_into_v in engine.hip: the out-projection is already inside the value rows).
+// The score matrix is never materialised (the reference writes B x N x N fp32: 1 GiB per sample at the 1024^2
+// patch windows): online softmax, fp32 running max / sum, exact rescale only when a row's max moved.
+//
+// Workgroup = 512 threads (8 wave64) = 128 queries of one sample; KV tiles of 64 keys.
+//   S phase  : wave w owns queries 16w .. 16w+15 against all 64 keys: S^T = K Q^T on v_mfma_f32_16x16x32
+//              (A = K rows from LDS, B = the wave's Q fragments, RESIDENT in 16 x 4 VGPRs for the whole kernel), so a
+//              lane holds 16 keys of ONE query: the row max / sum are in-lane + two wave shuffles, nothing crosses
+//              waves.  P (bf16 | fp16) goes to LDS together with the row's rescale factor.
+//   PV phase : wave (qh, dq) owns queries 64 qh .. +63 x channels 128 dq .. +127 of O^T = V't P^T on
+//              v_mfma_f32_32x32x16 (A = V't rows, B = P rows): 8 tiles = 128 accumulator registers.
+//   LDS      : K tile [64 keys][C] (64 KB) | V't tile [C][64 keys] (64 KB) | P [128][64] (16 KB) | row scalars.
+//              Both tiles arrive by LDS-DMA (global_load_lds, 16 B / lane) with the XOR swizzle on the SOURCE
+//              address; K(t+1) flies under PV(t), V't(t) under S(t): two barriers per KV tile.  (Requesting K(t+1) a phase
+//              earlier - third barrier after the S loop, counted vmcnt before PV - was measured: 5 % slower at N = 1296 and
+//              at N = 16384; K's latency is already covered by the PV phase, the barrier is not free.)
+// Epilogue: O / l + bias + residual -> zero-bordered NHWC bf16 + GroupNorm statistics of the output (stat_add).
+// Registers: O 128 + Q 64 of the 256 a wave has at two waves per SIMD; the S phase is software-pipelined by hand (the
+// fragment of step ks+1 is requested as soon as the MFMA of step ks has consumed its register: four LDS reads in
+// flight) and per-tile LDS offsets are re-formed per tile instead of living across phases - one spilled register
+// would put a scratch reload (a VMEM wait) into the loop and drain the LDS-DMA queue.
+// hipcc (ROCm 7.2) detail this kernel depends on: an LDS access whose memory operand carries no TBAA tag (a uint4 /
+// uint2 struct load, a bit_cast-wrapped load) is made to wait vmcnt(0) for every LDS-DMA in flight ("may alias"),
+// a typed ext_vector load / store is not - so every LDS fragment access below uses the MFMA operand vector types.
+// HALF selects fp16 operands (BASELINE configs[4] "fp16 attention MFMA path"): qkv / V't / P are then IEEE half.
+//
+// flash_attn2_kernel (round 5) is the round-2 kernel of this structure (flash_attn_kernel, retired: profiles/EXPERIMENTS.md) with every fragment
+// read of the two MFMA phases as INLINE ASM with COUNTED lgkmcnt waits.  hipcc's own LDS bookkeeping drains the queue (lgkmcnt(0)) every few
+// MFMAs, so both phases of the round-2 kernel were LDS-LATENCY bound: ~50 cycles per 16-cycle MFMA in the S phase, ~150 per 32-cycle MFMA in the PV phase (s_memtime
 // stamps), 9.4 k cycles per tile for 4.1 k of matrix work.  Here the S phase keeps four fragment reads (one k32 step) in flight under the four
 // MFMAs of the step before, the PV phase one whole k16 step (2 P + NC V't fragments); the row maximum of the softmax uses
 // v_permlane16_swap / v_permlane32_swap instead of two ds_bpermute round trips.
@@ -11,19 +39,56 @@
 // pipe-bound: each wave's own S + softmax chain was 1.9 k cycles per 32 keys whichever phase its partner was in, and with a single S wave per
 // SIMD nothing covers its LDS latency - 120-126 us against the 111 us of flash_attn_kernel at N = 1296, B = 16.  profiles/EXPERIMENTS.md.)
 #pragma once
-#include "flash_attn.hip.h"
+#include "cgemm.hip.h"
 #include "asmops.hip.h"
+
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
+typedef __attribute__((ext_vector_type(2))) uint32_t u32x2_t;
+
+struct FlashP {
+    const bf16_t* qkv; long long qkv_bstride; int ld;      // [B][N][ld], q at 0, k at C
+    const bf16_t* vt; long long vt_bstride; int Npad;      // [B][C][Npad]
+    int N, C, W;                                            // tokens, channels, image width (token n = pixel (n / W, n % W))
+    float scale_log2e;                                      // log2(e) / sqrt(C)
+    const float* bias;                                      // [C]
+    const bf16_t* res; long long res_bstride;               // x, zero-bordered NHWC
+    bf16_t* out; long long out_bstride;                     // y, zero-bordered NHWC
+    stat_t* stats_out;
+    int nq;                                                 // query tiles per sample
+    unsigned long long* dbg;                                // UCDIR_TIMING builds: s_memtime stamps of one wave
+};
+
+#ifdef UCDIR_TIMING
+#define FA_STAMP() do { if (dbg_on && dbg_n < 250) p.dbg[dbg_n++] = __builtin_amdgcn_s_memtime(); } while (0)
+#else
+#define FA_STAMP() do {} while (0)
+#endif
+
+#define FA_BQ 128
+#define FA_BK 64
+#define FA_THREADS 512
+
+__host__ __device__ constexpr int fa_lds_bytes(int C) { return FA_BK * C * 2 * 2 + FA_BQ * FA_BK * 2 + 2048; }
+
+template <bool HALF> struct FaVec { typedef bf16x8_t T; };
+template <> struct FaVec<true> { typedef f16x8_t T; };
+__device__ __forceinline__ f32x4_t fa_mfma16(const bf16x8_t& a, const bf16x8_t& b, f32x4_t c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ f32x4_t fa_mfma16(const f16x8_t& a, const f16x8_t& b, f32x4_t c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ f32x16_t fa_mfma32(const bf16x8_t& a, const bf16x8_t& b, f32x16_t c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ f32x16_t fa_mfma32(const f16x8_t& a, const f16x8_t& b, f32x16_t c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+template <bool HALF>
+__device__ __forceinline__ uint32_t fa_pack2(float lo, float hi) {
+    if constexpr (HALF) {
+        typedef __attribute__((ext_vector_type(2))) _Float16 h2;
+        h2 v; v[0] = (_Float16)lo; v[1] = (_Float16)hi;
+        return __builtin_bit_cast(uint32_t, v);
+    } else return pack2_bf16(lo, hi);
+}
 
 // LDS fragment read the compiler does not count (cdna guide 5.7 form iii), for either operand type
 template <int OFF, typename V>
 __device__ __forceinline__ void fa2_read16(V& v, unsigned addr) {
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-}
-
-// one LDS-DMA piece with a wave-uniform (SGPR) base and a 32-bit per-lane byte offset (conv_sk.hip.h's form: no 64-bit per-lane pointer - the pieces are
-// issued between the MFMAs now, where two more live registers per piece spilled at C = 512); M0 = the LDS destination, written inside the statement
-__device__ __forceinline__ void fa2_dma16(const void* sbase, unsigned voff, unsigned lds_dst) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(voff), "s"(sbase), "s"(lds_dst) : "memory", "m0");
 }
 
 // C = 128 * NC channels (NC = 1 .. 4); the head is the whole channel dimension
@@ -64,7 +129,8 @@ __global__ __launch_bounds__(FA_THREADS, 2) void flash_attn2_kernel(const FlashP
     // (round 6: one piece per call - the pieces of K(t + 1) and V't(t) are issued BETWEEN the MFMAs of the PV / S phase instead of as a block of
     // 2 NC instructions per wave at the phase's head.  s_memtime stamps: with every fragment read removed the PV phase still took 4.6 k cycles for 2 k of
     // matrix work - all eight waves issued their eight LDS-DMAs (~100 - 185 cycles each inside such a phase) at the same time and the matrix pipe sat
-    // idle meanwhile; spread out, one wave's DMA issue runs under its SIMD partner's MFMAs.)
+    // idle meanwhile; spread out, one wave's DMA issue runs under its SIMD partner's MFMAs.  The pieces go through dma16_sbase (asmops.hip.h): a 64-bit
+    // per-lane pointer per piece, live between the MFMAs, spilled at C = 512.)
     constexpr int NPIECE = 2 * NC;                     // DMA instructions per wave for a K tile, and for a V't tile (C / 64)
     auto issue_K_piece = [&](int t, int i) {
         constexpr int LPR = KROW / 16;                 // lanes per key row (64 | 48 | 32 | 16)
@@ -74,12 +140,12 @@ __global__ __launch_bounds__(FA_THREADS, 2) void flash_attn2_kernel(const FlashP
         if constexpr (LPR == 64) {                     // C = 512: one key row per instruction - the row is wave-uniform and goes into the SGPR base
             int kg = t * FA_BK + inst; kg = kg < N ? kg : N - 1;
             const unsigned char* rowp = kglob + (size_t)__builtin_amdgcn_readfirstlane(kg) * krow_bytes;
-            fa2_dma16(rowp, (unsigned)((ln ^ (inst & 15)) << 4), (unsigned)__builtin_amdgcn_readfirstlane(inst * 1024));
+            dma16_sbase(rowp, (unsigned)((ln ^ (inst & 15)) << 4), (unsigned)__builtin_amdgcn_readfirstlane(inst * 1024));
         } else {
             const int e = inst * 64 + ln, r = e / LPR, j = e - r * LPR;
             int kg = t * FA_BK + r; kg = kg < N ? kg : N - 1;
             const unsigned off = (unsigned)kg * krow_bytes + (unsigned)((j ^ (r & 15)) << 4);
-            fa2_dma16(kglob, off, (unsigned)__builtin_amdgcn_readfirstlane(inst * 1024));                     // (the K tile sits at LDS offset 0)
+            dma16_sbase(kglob, off, (unsigned)__builtin_amdgcn_readfirstlane(inst * 1024));                     // (the K tile sits at LDS offset 0)
         }
     };
     auto issue_K = [&](int t) {
@@ -96,7 +162,7 @@ __global__ __launch_bounds__(FA_THREADS, 2) void flash_attn2_kernel(const FlashP
         const unsigned off = (unsigned)(ln >> 3) * vrow_bytes + lc * 16;
         const int inst = i * 8 + wave;
         const unsigned char* rowp = vglob + (size_t)(inst * 8) * vrow_bytes + (size_t)t * (FA_BK * 2);         // wave-uniform
-        fa2_dma16(rowp, off, (unsigned)__builtin_amdgcn_readfirstlane(FA_BK * KROW + inst * 1024));
+        dma16_sbase(rowp, off, (unsigned)__builtin_amdgcn_readfirstlane(FA_BK * KROW + inst * 1024));
     };
 
 #ifdef UCDIR_TIMING
@@ -154,8 +220,8 @@ __global__ __launch_bounds__(FA_THREADS, 2) void flash_attn2_kernel(const FlashP
 #pragma unroll
         for (int kt = 0; kt < 4; ++kt) sacc[kt] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
         // fragment of (ks, kt): byte address ka[ks & 3] + (ks >> 2) 256 + kt 16 KROW - four per-lane registers (the swizzle XOR), the rest immediates.
-        // Inline-asm reads with counted lgkmcnt (hipcc's own bookkeeping drains the LDS queue - lgkmcnt(0) - every few MFMAs: flash_attn.hip.h
-        // runs this phase at ~50 cycles per 16-cycle MFMA).
+        // Inline-asm reads with counted lgkmcnt (hipcc's own bookkeeping drains the LDS queue - lgkmcnt(0) - every few MFMAs: the round-2 kernel ran
+        // this phase at ~50 cycles per 16-cycle MFMA).
         // (kbase has its low eight bits clear and kxor lives in bits 4 - 7: kbase + ((64 c4) ^ kxor) = (kbase | kxor) ^ (64 c4): ONE register and one
         // v_xor per k step instead of four address registers; dynamic LDS starts at byte 0 - no static __shared__ - and the K tile comes first)
         int kx = kxor;

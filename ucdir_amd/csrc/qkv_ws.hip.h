@@ -1,7 +1,7 @@
 // q, k, v' = conv1x1(GroupNorm(x)) of SelfAttention (model/ucdir.py:165-182) as a PERSISTENT, weight-stationary GEMM (gfx950).
 //
 //   [3C x C] (GroupNorm scale folded, v' = W_o W_v: fold_out_into_v) x [C x N pixels] per sample, N = H W.
-//   q, k -> qkv [B][N][ld] (q at 0, k at C), v' -> V't [B][C][Npad] TRANSPOSED, which is what flash_attn.hip.h stages by LDS-DMA:
+//   q, k -> qkv [B][N][ld] (q at 0, k at C), v' -> V't [B][C][Npad] TRANSPOSED, which is what flash_attn2.hip.h stages by LDS-DMA:
 //   the separate transpose_v_kernel launch (14 us x 6 per forward at B = 16) and its round trip through HBM are gone.
 //
 // Why (round 3): the shifted-GEMM kernel (cgemm_kernel<128, std, s1>) ran this K = 512 product at 410 TFLOP/s (79 us per B = 16
