@@ -294,20 +294,38 @@ def resblock_dy3h_emu(sd: SD, p: str, srcs: Sequence[torch.Tensor], temb: torch.
     return h + res
 
 
-def self_attention_emu(sd: SD, p: str, x32: torch.Tensor, rnd: bool) -> torch.Tensor:
+def _rh(t: torch.Tensor, rnd: bool = True) -> torch.Tensor:
+    """Round to IEEE half (round to nearest even), back to fp32."""
+    return t.to(torch.float16).float() if rnd else t
+
+
+def self_attention_emu(sd: SD, p: str, x32: torch.Tensor, rnd: bool, attn_dtype: str = "bf16",
+                       scores: bool = False) -> torch.Tensor:
     """SelfAttention.forward (model/ucdir.py:165-182) as the engine evaluates it: the out projection folded into the value rows
-    (fp64 product, one rounding), q / k / v' and the probabilities as bf16, fp32 accumulation."""
+    (fp64 product, one rounding), q / k / v' and the probabilities rounded to ``attn_dtype``, fp32 accumulation.
+    ``attn_dtype="fp16"``: the engine's ``attn_fp16`` path - the weights stay bf16 (the GroupNorm-folded qkv GEMM is the bf16 one),
+    its q / k / v' output is stored as IEEE half, and the flash kernel rounds its unnormalised probabilities to half.
+    ``scores``: the materialised-score path (bf16 only) - P = softmax normalised in fp32, THEN rounded to bf16, and P V' is not
+    divided afterwards; the flash kernel instead rounds exp(s - m) and divides the fp32 accumulator by the fp32 row sum."""
+    if attn_dtype not in ("bf16", "fp16"):
+        raise ValueError(attn_dtype)
+    if scores and attn_dtype != "bf16":
+        raise ValueError("the materialised-score path has no fp16 operands")
+    ro = _rh if attn_dtype == "fp16" else _rb
     B, C, H, W = x32.shape
     xb = _rb(x32, rnd)
     mean, rstd = _mean_rstd([x32])
     wqkv = sd[p + "qkv.weight"].reshape(3 * C, C)
     wv2 = (sd[p + "out.weight"].reshape(C, C).double() @ wqkv[2 * C:].double()).float()
     wf = torch.cat([wqkv[:2 * C], wv2]).reshape(3 * C, C, 1, 1)
-    qkv = _rb(_fold_conv(xb, mean, rstd, wf, None, sd[p + "norm.weight"], sd[p + "norm.bias"], rnd), rnd)
+    qkv = ro(_fold_conv(xb, mean, rstd, wf, None, sd[p + "norm.weight"], sd[p + "norm.bias"], rnd), rnd)
     q, k, v = qkv.reshape(B, 3, C, H * W).unbind(dim=1)
     s = torch.bmm(q.transpose(1, 2), k) / math.sqrt(C)
     pr = torch.exp(s - s.max(dim=-1, keepdim=True).values)
-    out = torch.bmm(v, _rb(pr, rnd).transpose(1, 2)) / pr.sum(dim=-1).unsqueeze(1)
+    if scores:
+        out = torch.bmm(v, _rb(pr / pr.sum(dim=-1, keepdim=True), rnd).transpose(1, 2))
+    else:
+        out = torch.bmm(v, ro(pr, rnd).transpose(1, 2)) / pr.sum(dim=-1).unsqueeze(1)
     return out.reshape(B, C, H, W) + sd[p + "out.bias"].view(1, -1, 1, 1) + xb
 
 
@@ -326,9 +344,13 @@ def _upconv_emu(xb: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, rnd: bool
 
 
 def dy3h_naive_forward_emu(sd: SD, x: torch.Tensor, level: torch.Tensor, guide: torch.Tensor, prefix: str = "denoise_fn.",
-                           taps: Optional[dict] = None, rnd: bool = True, force: Optional[dict] = None) -> torch.Tensor:
+                           taps: Optional[dict] = None, rnd: bool = True, force: Optional[dict] = None,
+                           attn_dtype: str = "bf16") -> torch.Tensor:
     """DY3h.naiveforward (model/ucdir.py:270-293) with bf16 rounding where ucdir_amd/csrc rounds (``rnd=False``: no rounding,
-    equal to dy3h_naive_forward up to fp32 re-association).
+    equal to dy3h_naive_forward up to fp32 re-association).  ``attn_dtype="fp16"``: the attention operands as the engine's
+    ``attn_fp16`` path rounds them (self_attention_emu).
+    ``taps`` and ``force`` only need item assignment, and ``in`` / item lookup: a caller may pass objects that compute a
+    metric on assignment and read each forced activation on demand instead of holding every layer at once.
     ``force`` (teacher forcing, for per-layer checks): {tap name: tensor}.  After a layer's own output has been recorded in ``taps``,
     the network CONTINUES from ``force[name]`` (the activation another implementation stored for that layer) instead of its own
     value - every layer is then evaluated on the other implementation's inputs, and what is left between the two per layer is
@@ -345,7 +367,7 @@ def dy3h_naive_forward_emu(sd: SD, x: torch.Tensor, level: torch.Tensor, guide: 
     def run_block(base, srcs):
         y = resblock_dy3h_emu(sd, base + "res_block.", srcs, temb, guide, rnd, taps, force)
         if (base + "attn.qkv.weight") in sd:
-            y = self_attention_emu(sd, base + "attn.", y, rnd)
+            y = self_attention_emu(sd, base + "attn.", y, rnd, attn_dtype)
         return forced(base[:-1], y)
 
     for kind, base in downs:

@@ -8,6 +8,10 @@ fp32 accumulation and stores activations in bf16, so vs the fp32 oracle we expec
     bf16-emulation mode (oracle.dy3h_naive_forward_emu: rounding where the kernels round) sits at 1.47-1.50e-2 from the fp32 oracle on the
     same inputs, i.e. the whole difference IS the numerics plan; bound FWD_TOL = 1.7e-2 (tests/test_hip_gpu.py)
   * one layer against the emulation on the HIP path's own input activations (layerwise_emu_case): <= 6.7e-4 measured, bound 2e-3
+Every metric above is a global rel-RMS, which dilutes an error confined to one tile, strip column or sample-boundary row of
+a large layer.  metrics() therefore also reports, for 4-D tensors, ``tile_max`` (the worst RMS error of one block of
+1 sample x 64 channels x 32 x 32 positions, relative to the GLOBAL reference RMS) and ``elem_max`` (the worst single element,
+same scale); tests/test_tile_metric_cpu.py shows which modelled faults each bound catches.
 """
 import ctypes
 import math
@@ -22,6 +26,20 @@ from ucdir_amd.spec import UNetConfig
 from ucdir_amd.weights import synth_inputs, synth_state_dict
 
 DEV = "cuda"
+
+EMU_LAYER_TOL = 2e-3   # one layer of the HIP path against the oracle's bf16-emulation mode ON THE SAME INPUTS (teacher forcing): what is left is
+                       # fp32 summation order and single bf16 rounding flips.  Measured (tools/_emu_probe.py): worst layer 6.7e-4 (full SID, B = 1),
+                       # 4.4e-4 (B = 4), 8.9e-4 (small configuration) - the attention blocks of the 18^2 / 36^2 levels; everything else <= 4e-4
+TILE = (64, 32, 32)    # (channels, rows, columns) of one tile_max block; one sample per block
+# tile-local bounds (metrics() keys tile_max / elem_max) and the attention-vs-emulation bounds: each about 1.5x the worst value
+# measured on the MI355X over every case that asserts it; tests/test_tile_metric_cpu.py shows the modelled faults exceed them
+OP_TILE_TOL = 4e-3     # single operator vs torch: worst 2.61e-3 (test_conv_stream_k_with_res_conv[level4_ksplit], the res_conv output)
+OP_ELEM_TOL = 5.5e-2   # ... worst 3.65e-2 (test_akgm_block_kernel_at_narrow_groups[cg8_th8]): one bf16 step of a large output
+EMU_TILE_TOL = 1.3e-3  # one layer vs the emulation: worst 8.84e-4 (full SID B = 1, an attention block at 36^2); B = 32: 6.3e-4,
+                       # 1024^2 windows: 4.3e-4, fp16 attention windows: 4.2e-4 (tests/test_layerwise_gpu.py)
+ATT_EMU_TOL = 2.5e-3   # attention vs self_attention_emu, rel-RMS of the branch: worst 1.62e-3 (C = 384, N = 4096, flash)
+ATT_EMU_TILE_TOL = 3e-3  # ... worst 1.98e-3 (C = 512, N = 1296, B = 2, flash)
+ATT_EMU_ELEM_TOL = 6e-2  # ... worst 3.90e-2 (C = 512, N = 16384, flash)
 
 
 def bfr(t):
@@ -40,13 +58,56 @@ def _st():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def tile_metrics(d, rms):
+    """Tile-local view of the difference ``d`` (B, C, H, W) against a reference of global RMS ``rms``: ``tile_max`` = max over
+    blocks of one sample x TILE of sqrt(mean(d^2 over the block)) / rms (ragged edge blocks divide by their true element
+    count), ``tile_at`` = (sample, channel, row, column) of that block's first element, ``elem_max`` = max |d| / rms."""
+    B, Cc, H, W = d.shape
+    tc, th, tw = TILE
+    nc, nh, nw = -(-Cc // tc), -(-H // th), -(-W // tw)
+    sums = torch.zeros(B, nc, nh, nw, dtype=torch.float64)
+    for b in range(B):                       # one sample at a time: a 1024^2 layer is 270 MB per sample
+        for ci in range(nc):
+            blk = d[b, ci * tc:(ci + 1) * tc].pow(2)
+            if nh * th != H or nw * tw != W:
+                blk = F.pad(blk, (0, nw * tw - W, 0, nh * th - H))
+            sums[b, ci] = blk.reshape(blk.shape[0], nh, th, nw, tw).sum(dim=(0, 2, 4)).double()
+    cnt = lambda n, t, k: torch.tensor([min(t, n - i * t) for i in range(k)], dtype=torch.float64)
+    count = cnt(Cc, tc, nc).view(nc, 1, 1) * cnt(H, th, nh).view(1, nh, 1) * cnt(W, tw, nw).view(1, 1, nw)
+    tile = (sums / count).sqrt() / max(rms, 1e-12)
+    i = int(tile.flatten().argmax())
+    b, r = divmod(i, nc * nh * nw)
+    ci, r = divmod(r, nh * nw)
+    hi, wi = divmod(r, nw)
+    return {"tile_max": float(tile.flatten()[i]), "tile_at": (b, ci * tc, hi * th, wi * tw),
+            "elem_max": float(d.abs().max()) / max(rms, 1e-12)}
+
+
 def metrics(got, ref):
     got = got.detach().float().cpu()
     ref = ref.detach().float().cpu()
     d = got - ref
     rms = ref.pow(2).mean().sqrt().item()
-    return {"rel_rms": (d.pow(2).mean().sqrt().item() / max(rms, 1e-12)), "max_abs": d.abs().max().item(),
-            "ref_rms": rms, "nan": bool(torch.isnan(got).any())}
+    m = {"rel_rms": (d.pow(2).mean().sqrt().item() / max(rms, 1e-12)), "max_abs": d.abs().max().item(),
+         "ref_rms": rms, "nan": bool(torch.isnan(got).any())}
+    if d.dim() == 4:
+        m.update(tile_metrics(d, rms))
+    return m
+
+
+def profile_keys(L, fn):
+    """Run fn() with the library's per-launch event profiler on and return {key: launches} of the kernels it dispatched."""
+    ulib.check(L.ucdir_profile_enable(1))
+    try:
+        r = fn()
+    finally:
+        ulib.check(L.ucdir_profile_enable(0))
+    cap = 64
+    keys, ln = (ctypes.c_int32 * cap)(), (ctypes.c_int32 * cap)()
+    ms, fl, by = (ctypes.c_double * cap)(), (ctypes.c_double * cap)(), (ctypes.c_double * cap)()
+    nr = ctypes.c_int32(0)
+    ulib.check(L.ucdir_profile_read(cap, keys, ln, ms, fl, by, ctypes.byref(nr), _st()))
+    return r, {int(keys[i]): int(ln[i]) for i in range(nr.value)}
 
 
 def rng(seed):
@@ -125,6 +186,7 @@ def conv_res_case(B, H, W, c0, c1, cout, seed=0):
     m = metrics(dy, y)
     mr = metrics(dyr, yr)
     m["res_rel_rms"], m["res_nan"] = mr["rel_rms"], mr["nan"]
+    m["res_tile_max"], m["res_elem_max"] = mr["tile_max"], mr["elem_max"]
     got = dy.double().cpu()
     st_ref = np.stack([got.sum(dim=(1, 2, 3)).numpy(), got.pow(2).sum(dim=(1, 2, 3)).numpy()], 1)
     m["stats_rel"] = float(np.abs(stats - st_ref).max() / np.abs(st_ref).max())
@@ -172,10 +234,7 @@ def attention_case(B, C, H, W, seed=0, fp16=False, flash=1):
     L = ulib.load()
     g = rng(seed)
     x = bfr(torch.randn(B, C, H, W, generator=g) * 1.2 + 0.3)
-    sd = {"a.norm.weight": 1 + 0.25 * torch.randn(C, generator=g), "a.norm.bias": 0.2 * torch.randn(C, generator=g),
-          "a.qkv.weight": torch.randn(3 * C, C, 1, 1, generator=g) * math.sqrt(3.0 / C),
-          "a.out.weight": torch.randn(C, C, 1, 1, generator=g) * math.sqrt(1.5 / C),
-          "a.out.bias": torch.randn(C, generator=g) * 0.1}
+    sd = attention_weights(C, g)
     y = O.self_attention(sd, "a.", x)
     dy = torch.empty(B, C, H, W, device=DEV)
     n = lambda k: sd[k].numpy().copy()
@@ -193,6 +252,131 @@ def attention_case(B, C, H, W, seed=0, fp16=False, flash=1):
     branch = y - x
     m["rel_rms_branch"] = float(((dy.cpu() - y).pow(2).mean().sqrt() / branch.pow(2).mean().sqrt()).item())
     return m
+
+
+def attention_weights(C, g):
+    return {"a.norm.weight": 1 + 0.25 * torch.randn(C, generator=g), "a.norm.bias": 0.2 * torch.randn(C, generator=g),
+            "a.qkv.weight": torch.randn(3 * C, C, 1, 1, generator=g) * math.sqrt(3.0 / C),
+            "a.out.weight": torch.randn(C, C, 1, 1, generator=g) * math.sqrt(1.5 / C),
+            "a.out.bias": torch.randn(C, generator=g) * 0.1}
+
+
+def last_token_share(x, sd):
+    """Mean over the query rows of the softmax weight the LAST key gets (fp32 oracle algebra, model/ucdir.py:165-182)."""
+    B, C, H, W = x.shape
+    h = F.group_norm(x, 1, sd["a.norm.weight"], sd["a.norm.bias"], eps=1e-5).reshape(B, C, H * W)
+    w = sd["a.qkv.weight"].reshape(3 * C, C)
+    q, k = w[:C] @ h, w[C:2 * C] @ h
+    return float(torch.softmax(torch.bmm(q.transpose(1, 2), k) / math.sqrt(C), dim=-1)[..., -1].mean())
+
+
+def masking_attention_inputs(B, C, H, W, seed=0, share=0.4):
+    """Attention inputs on which a masking error of the LAST key or query moves the output by far more than 1 / N: every
+    token carries a common channel direction e, the last token in addition a large distinct direction f (its value row and
+    its residual differ from every other token's), and rank-1 terms in the q / k weights (q_i ~ u for every token, k ~ u for
+    the last token only) give the last key about ``share`` of every row's softmax mass, whatever N.  A clamped duplicate of
+    key N - 1 counted once more then moves every row's branch by p (1 - p) / (1 + p) |v'(N - 1) - v'(rest)| (p = share; 0.17
+    at p = 0.4, the maximum) instead of the ~1 / N a random input gives (tests/test_tile_metric_cpu.py)."""
+    g = rng(seed)
+    N = H * W
+    e = torch.randn(C, generator=g); e -= e.mean(); e /= e.norm()
+    f = torch.randn(C, generator=g); f -= f.mean(); f -= (f @ e) * e; f /= f.norm()
+    u = torch.randn(C, generator=g); u /= u.norm()
+    x = 0.5 * torch.randn(B, C, N, generator=g) + 2.0 * math.sqrt(C) * e.view(1, C, 1)
+    x[:, :, N - 1] += 4.0 * math.sqrt(C) * f
+    x = bfr(x.view(B, C, H, W))
+    sd = attention_weights(C, g)
+    sd["a.norm.bias"].zero_()
+    sd["a.norm.weight"].fill_(1.0)
+    w = sd["a.qkv.weight"].view(3 * C, C)
+    w[:C] += 2.0 * torch.outer(u, e)                               # q_i ~ 2 u for every token
+    base = w[C:2 * C].clone()
+    lo, hi = -64.0, 64.0                                           # k(N - 1) ~ a u: bisect a for the wanted share
+    for _ in range(40):
+        a = 0.5 * (lo + hi)
+        w[C:2 * C] = base + a * torch.outer(u, f)
+        lo, hi = (a, hi) if last_token_share(x, sd) < share else (lo, a)
+    w[C:2 * C] = base + 0.5 * (lo + hi) * torch.outer(u, f)
+    return x, sd
+
+
+def attention_emu_case(B, C, H, W, seed=0, fp16=False, flash=1, masking=False):
+    """ucdir_op_attention against oracle.self_attention_emu on the same bf16 input (rounding where the kernels round, fp32
+    accumulation; fp16: the attn_fp16 rounding points).  The emulation follows the path the engine took (profiler key 130 / 131
+    = the flash kernel, otherwise the materialised-score path, which rounds the NORMALISED probabilities: scores=True).
+    Metrics on the attention branch (output minus the residual input, both sides), the emulation rounded to bf16 like the
+    stored output.  ``masking``: masking_attention_inputs instead of random ones."""
+    L = ulib.load()
+    if masking:
+        x, sd = masking_attention_inputs(B, C, H, W, seed)
+    else:
+        g = rng(seed)
+        x = bfr(torch.randn(B, C, H, W, generator=g) * 1.2 + 0.3)
+        sd = attention_weights(C, g)
+    dy = torch.empty(B, C, H, W, device=DEV)
+    n = lambda k: sd[k].numpy().copy()
+    dx = x.to(DEV)
+    hp = [n(k) for k in ("a.norm.weight", "a.norm.bias", "a.qkv.weight", "a.out.weight", "a.out.bias")]
+
+    def run():
+        ulib.check(L.ucdir_op_attention(_p(dx), B, C, H, W, *[_hp(a) for a in hp], int(fp16), _p(dy), _st()))
+        torch.cuda.synchronize()
+    ulib.check(L.ucdir_debug_flag(b"flash", flash))
+    try:
+        _, keys = profile_keys(L, run)
+    finally:
+        ulib.check(L.ucdir_debug_flag(b"flash", -1))
+    is_flash = (131 if fp16 else 130) in keys
+    e = bfr(O.self_attention_emu(sd, "a.", x, True, "fp16" if fp16 else "bf16", scores=not is_flash))
+    m = metrics(dy.cpu() - x, e - x)
+    m["flash"] = is_flash
+    if masking:
+        m["last_share"] = last_token_share(x, sd)
+    return m
+
+
+class HipLayers:
+    """One sample of the last HIP forward, layer by layer, for oracle.dy3h_naive_forward_emu without holding the network on the
+    host: as ``force`` it reads a stored activation (debug_read, sliced to the sample on the device) when the emulation asks
+    for it; as ``taps`` it compares the emulated layer output (bf16-rounded, like the stored one) with it and keeps only the
+    metrics (``self.out``).  No other forward may run on the network while it is in use: debug_read reads the last one."""
+
+    def __init__(self, dn, b, prefix="denoise_fn."):
+        from ucdir_amd.spec import unet_layers
+        self.dn, self.b, self.out, self._last = dn, b, {}, (None, None)
+        self.names = {}
+        for Ld in unet_layers(dn.cfg):
+            self.names[prefix + Ld.name] = (Ld.name, Ld.name, "out")
+            if Ld.kind == "block":
+                self.names[prefix + Ld.name + ".res_block.h1"] = (Ld.name + ":h1", Ld.name, "h1")
+
+    def __contains__(self, key):
+        return key in self.names
+
+    def __getitem__(self, key):
+        if self._last[0] != key:
+            _, layer, what = self.names[key]
+            t = self.dn.debug_read(layer, what)[self.b:self.b + 1].float().cpu()
+            torch.cuda.synchronize()
+            self._last = (key, t)
+        return self._last[1]
+
+    def __setitem__(self, key, y):
+        if key in self.names:
+            self.out[self.names[key][0]] = metrics(self[key], bfr(y))
+
+
+def layerwise_emu_sample(dn, sd, x6, lvl, guide, b, pad, attn_dtype="bf16"):
+    """Layer-wise metrics of sample ``b`` of the LAST forward of ``dn`` (x6, lvl, guide: that forward's host inputs; ``pad``:
+    the forward reflect-padded them by pad32 like forward_split, else they are already multiples of 32) against the emulation
+    fed with the HIP path's own activations.  Returns {layer or layer:h1: metrics}."""
+    xs, gs = x6[b:b + 1], guide[b:b + 1]
+    if pad:
+        ph, pw = O.pad32(x6.shape[-2]), O.pad32(x6.shape[-1])
+        xs, gs = F.pad(xs, (0, pw, 0, ph), mode="reflect"), F.pad(gs, (0, pw, 0, ph), mode="reflect")
+    hl = HipLayers(dn, b)
+    O.dy3h_naive_forward_emu(sd, xs, lvl[b:b + 1], gs, taps=hl, force=hl, attn_dtype=attn_dtype)
+    return hl.out
 
 
 def build_net(cfg: UNetConfig, seed=0):

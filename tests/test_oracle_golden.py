@@ -172,13 +172,17 @@ def test_bf16_emulation_mode_is_the_same_network(cfg):
     lvl = torch.tensor([[0.3], [0.7]])
     ta, tb = {}, {}
     a = O.dy3h_naive_forward(sd, x6, lvl, guide, taps=ta)
-    b = O.dy3h_naive_forward_emu(sd, x6, lvl, guide, taps=tb, rnd=False)
     rel = lambda u, v: float((u - v).pow(2).mean().sqrt() / v.pow(2).mean().sqrt())
-    assert rel(b, a) < 1e-5, rel(b, a)
-    assert set(tb) == set(ta)
-    for k in ta:
-        assert rel(tb[k], ta[k]) < 1e-5, (k, rel(tb[k], ta[k]))
+    for attn_dtype in ("bf16", "fp16"):                    # the fp16-attention mode (attn_fp16) is the same network too
+        tb = {}
+        b = O.dy3h_naive_forward_emu(sd, x6, lvl, guide, taps=tb, rnd=False, attn_dtype=attn_dtype)
+        assert rel(b, a) < 1e-5, (attn_dtype, rel(b, a))
+        assert set(tb) == set(ta)
+        for k in ta:
+            assert rel(tb[k], ta[k]) < 1e-5, (attn_dtype, k, rel(tb[k], ta[k]))
     c = O.dy3h_naive_forward_emu(sd, x6, lvl, guide, rnd=True)
     assert 1e-3 < rel(c, a) < 2e-2, rel(c, a)
+    c16 = O.dy3h_naive_forward_emu(sd, x6, lvl, guide, rnd=True, attn_dtype="fp16")
+    assert 1e-3 < rel(c16, a) < 2e-2 and not torch.equal(c16, c), rel(c16, a)
     d = O.dy3h_forward(sd, x6, lvl, guide, emulate_bf16=True)             # the pad-32 wrapper routes to the same function
     assert d.shape == a.shape and 1e-3 < rel(d, O.dy3h_forward(sd, x6, lvl, guide)) < 2e-2
