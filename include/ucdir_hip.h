@@ -202,6 +202,11 @@ int32_t ucdir_predictor_load_weight(ucdir_predictor* p, const char* name, const 
 int32_t ucdir_predictor_finalize(ucdir_predictor* p);
 int32_t ucdir_predictor_forward(ucdir_predictor* p, const float* x, float* y, int32_t B, int32_t H, int32_t W,
                                 void* stream);
+/* Copy an activation of the last predictor forward into dst as (B,C,Hc>>l,Wc>>l) fp32 NCHW (tests), on the padded compute
+ * grid Hc = (H/32+1)*32, Wc likewise.  name = the reference module: "conv{l}_1" / "conv{l}_2" (after LeakyReLU, l = 1..9),
+ * "pool{l}" (l = 1..4), "upv{l}" (l = 6..9).  C is the CARRIED channel count: 64 for the 32-channel layers, whose upper
+ * half is zero.  Unknown names and a wrong dst_elems are errors. */
+int32_t ucdir_predictor_debug_read(ucdir_predictor* p, const char* name, float* dst, int64_t dst_elems, void* stream);
 
 /* ---- single-operator entry points (unit parity tests; fp32 NCHW in/out, bf16 inside) -----
  * conv: y = act(conv(GN?(cat[x0,x1]))) with 3x3 (mode 0 stride 1, 1 stride-2 down,

@@ -464,6 +464,50 @@ def predictor_forward(sd: SD, x: torch.Tensor, prefix: str = "predictor.") -> to
     return out[..., :-ph, :-pw]
 
 
+# The engine's rounding points for the predictor (ucdir_amd/csrc/engine.hip, predictor_forward):
+#   * conv1_1 (stem_mfma_kernel<3, 2>): the reflect-extended input and the weights as bf16, the bias as bf16 hi + lo parts;
+#   * every 3x3 conv (conv3x3_halo / conv_ws / conv_sk): bf16 weights and (stored) inputs, fp32 accumulation, bias and LeakyReLU;
+#   * upv{l} (cgemm, 1x1 GEMM with a pixel-shuffle store): bf16 weights, fp32 bias, no activation;
+#   * every stored activation is rounded to bf16 once; max pooling of bf16 values is exact;
+#   * conv10_1 (cgemm, fp32 NCHW store): bf16 weights and input, fp32 bias and output.
+def predictor_forward_emu(sd: SD, x: torch.Tensor, taps: Optional[dict] = None, force: Optional[dict] = None, rnd: bool = True,
+                          prefix: str = "predictor.") -> torch.Tensor:
+    """predictor_forward with bf16 rounding where the kernels round (``rnd=False``: none, equal to predictor_forward up to fp32
+    re-association).  ``taps`` / ``force`` as in dy3h_naive_forward_emu, keyed by the module names conv{l}_1, conv{l}_2 (after
+    the LeakyReLU), pool{l} and upv{l}; tapped values are the fp32 ones before the store's rounding, on the padded grid."""
+    _, _, h, w = x.shape
+    ph, pw = pad32(h), pad32(w)
+    lrelu = lambda t: torch.max(0.2 * t, t)
+    P = lambda n: sd[prefix + n]
+
+    def forced(name, y):
+        if taps is not None:
+            taps[name] = y
+        return force[name] if (force is not None and name in force) else y
+
+    def c3(t, n):
+        return forced(n, lrelu(F.conv2d(_rb(t, rnd), _rb(P(n + ".weight"), rnd), P(n + ".bias"), padding=1)))
+
+    b1 = P("conv1_1.bias")
+    b1 = _rb(b1, rnd) + _rb(b1 - _rb(b1, rnd), rnd)
+    t = forced("conv1_1", lrelu(F.conv2d(_rb(F.pad(x, (0, pw, 0, ph), mode="reflect"), rnd), _rb(P("conv1_1.weight"), rnd), b1,
+                                         padding=1)))
+    enc = []
+    for lvl in range(1, 5):
+        if lvl > 1:
+            t = c3(t, f"conv{lvl}_1")
+        t = c3(t, f"conv{lvl}_2")
+        enc.append(t)
+        t = forced(f"pool{lvl}", F.max_pool2d(_rb(t, rnd), 2))
+    t = c3(c3(t, "conv5_1"), "conv5_2")
+    for lvl in range(6, 10):
+        t = forced(f"upv{lvl}", F.conv_transpose2d(_rb(t, rnd), _rb(P(f"upv{lvl}.weight"), rnd), P(f"upv{lvl}.bias"), stride=2))
+        t = c3(torch.cat([t, enc.pop()], dim=1), f"conv{lvl}_1")
+        t = c3(t, f"conv{lvl}_2")
+    out = F.conv2d(_rb(t, rnd), _rb(P("conv10_1.weight"), rnd), P("conv10_1.bias"))
+    return out[..., :-ph, :-pw]
+
+
 # ----------------------------------------------------------------------------------------------
 # sampler (model/diffusion.py:150-211, 473-478)
 # ----------------------------------------------------------------------------------------------

@@ -37,6 +37,10 @@ OP_TILE_TOL = 4e-3     # single operator vs torch: worst 2.61e-3 (test_conv_stre
 OP_ELEM_TOL = 5.5e-2   # ... worst 3.65e-2 (test_akgm_block_kernel_at_narrow_groups[cg8_th8]): one bf16 step of a large output
 EMU_TILE_TOL = 1.3e-3  # one layer vs the emulation: worst 8.84e-4 (full SID B = 1, an attention block at 36^2); B = 32: 6.3e-4,
                        # 1024^2 windows: 4.3e-4, fp16 attention windows: 4.2e-4 (tests/test_layerwise_gpu.py)
+EMU_ELEM_TOL = 6.5e-2  # ... one element (asserted by tests/test_predictor_gpu.py): worst 4.19e-2 (conv8_2, B = 16 at 384^2); the predictor's
+                       # layers against its emulation: rel-RMS <= 1.04e-4, tile_max <= 3.46e-4 (all shapes; no GroupNorm to amplify rounding)
+PRED_TILE_TOL = 1e-2   # the whole predictor vs the fp32 oracle (test_predictor, 3 channels x 32 x 32 blocks): worst 6.79e-3 (B = 2, 64 x 96)
+PRED_ELEM_TOL = 6e-2   # ... worst 3.93e-2 (1 x 256^2)
 ATT_EMU_TOL = 2.5e-3   # attention vs self_attention_emu, rel-RMS of the branch: worst 1.62e-3 (C = 384, N = 4096, flash)
 ATT_EMU_TILE_TOL = 3e-3  # ... worst 1.98e-3 (C = 512, N = 1296, B = 2, flash)
 ATT_EMU_ELEM_TOL = 6e-2  # ... worst 3.90e-2 (C = 512, N = 16384, flash)
@@ -114,8 +118,11 @@ def rng(seed):
     return torch.Generator().manual_seed(seed)
 
 
-def conv_case(B, H, W, c0, c1, cout, ksize, mode, gn, silu, residual, seed=0):
-    """ucdir_op_conv vs torch on bf16-representable inputs."""
+def conv_case(B, H, W, c0, c1, cout, ksize, mode, gn, act, residual, seed=0):
+    """ucdir_op_conv vs torch on bf16-representable inputs.  ``act``: 0 none, 1 swish, 2 LeakyReLU(0.2) (the predictor's
+    epilogue); True / False mean 1 / 0.  ``neg_frac``: the share of negative pre-activations in the reference."""
+    act = int(act)
+    assert act in (0, 1, 2), act
     L = ulib.load()
     g = rng(seed)
     cin = c0 + c1
@@ -136,8 +143,11 @@ def conv_case(B, H, W, c0, c1, cout, ksize, mode, gn, silu, residual, seed=0):
         y = F.conv2d(F.interpolate(h, scale_factor=2, mode="nearest"), w, b, padding=1)
     else:
         y = F.conv2d(h, w, b, padding=ksize // 2)
-    if silu:
+    neg_frac = float((y < 0).float().mean())
+    if act == 1:
         y = O.swish(y)
+    elif act == 2:
+        y = torch.max(0.2 * y, y)
     if residual:
         y = y + res
     # device
@@ -148,9 +158,10 @@ def conv_case(B, H, W, c0, c1, cout, ksize, mode, gn, silu, residual, seed=0):
     wn, bn = w.numpy().copy(), b.numpy().copy()
     gn_, bt_ = (gamma.numpy().copy(), beta.numpy().copy()) if gn else (None, None)
     ulib.check(L.ucdir_op_conv(_p(dx0), c0, _p(dx1), c1, B, H, W, _hp(wn), _hp(bn), _hp(gn_), _hp(bt_), cout, ksize,
-                               mode, int(silu), _p(dres), _p(dy), _hp(stats), _st()))
+                               mode, act, _p(dres), _p(dy), _hp(stats), _st()))
     torch.cuda.synchronize()
     m = metrics(dy, y)
+    m["neg_frac"] = neg_frac
     ref_stats = np.stack([y.double().sum(dim=(1, 2, 3)).numpy(), y.double().pow(2).sum(dim=(1, 2, 3)).numpy()], 1)
     m["stats_rel"] = float(np.abs(stats - ref_stats).max() / np.abs(ref_stats).max())
     # border vs interior error (a wrong GroupNorm border class shows up here)
@@ -506,6 +517,73 @@ def predictor_case(B, H, W, seed=3, net_sd=None):
         got = net.predictor(x.to(DEV))
     torch.cuda.synchronize()
     return metrics(got, ref)
+
+
+# the predictor's activations in forward order, by the reference's module names (UNetSeeInDark.debug_read)
+PREDICTOR_LAYERS = (["conv1_1", "conv1_2", "pool1"] + [n for l in range(2, 5) for n in (f"conv{l}_1", f"conv{l}_2", f"pool{l}")]
+                    + ["conv5_1", "conv5_2"] + [n for l in range(6, 10) for n in (f"upv{l}", f"conv{l}_1", f"conv{l}_2")])
+
+
+def emu_layer_ok(m):
+    """The bounds one teacher-forced layer of the HIP path must meet against the emulation (global, tile-local, element)."""
+    return (not m["nan"]) and m["rel_rms"] < EMU_LAYER_TOL and m["tile_max"] < EMU_TILE_TOL and m["elem_max"] < EMU_ELEM_TOL
+
+
+def predictor_real_channels(name):
+    """Real channel count of a predictor activation (the engine carries the 32-channel ones as 64)."""
+    l = int(name[-1]) if name.startswith(("pool", "upv")) else int(name[4])
+    lvl = l - 1 if name.startswith("pool") else (9 - l if name.startswith("upv") or l > 5 else l - 1)
+    return 32 << lvl
+
+
+class PredictorLayers:
+    """One sample of the last HIP predictor forward, layer by layer, for oracle.predictor_forward_emu (the HipLayers protocol):
+    as ``force`` it reads the stored activation (UNetSeeInDark.debug_read, sliced to the sample and to the real channels); as
+    ``taps`` it keeps only the metrics of the emulated layer (bf16-rounded, like the stored one) against it.  Every read also
+    checks that the stored values are finite and that the upper half of a 32-channel layer carried as 64 is exactly zero
+    (``self.upper``: {layer: max |upper half|}, ``self.finite``: {layer: bool})."""
+
+    def __init__(self, pred, b):
+        self.pred, self.b, self.out, self.upper, self.finite, self._last = pred, b, {}, {}, {}, (None, None)
+
+    def __contains__(self, key):
+        return key in PREDICTOR_LAYERS
+
+    def __getitem__(self, key):
+        if self._last[0] != key:
+            full = self.pred.debug_read(key)[self.b:self.b + 1]
+            real = predictor_real_channels(key)
+            self.finite[key] = bool(torch.isfinite(full).all())
+            if full.shape[1] > real:
+                self.upper[key] = float(full[:, real:].abs().max())
+            t = full[:, :real].float().cpu()
+            del full
+            torch.cuda.synchronize()
+            self._last = (key, t)
+        return self._last[1]
+
+    def __setitem__(self, key, y):
+        if key in PREDICTOR_LAYERS:
+            self.out[key] = metrics(self[key], bfr(y))
+
+
+def predictor_emu_case(net, sd, B, H, W, seed=3, samples=None):
+    """UNetSeeInDark on the HIP engine, layer by layer, against oracle.predictor_forward_emu fed with the HIP path's own
+    activations (teacher forcing), per sample in ``samples`` (default: all): {sample: {layer | "out": metrics}}, plus the upper
+    halves / finiteness PredictorLayers checked.  "out" = conv10_1 (fp32 output, cropped) on the HIP path's conv9_2."""
+    x = torch.from_numpy(synth_inputs(B, H, W, seed=seed)[0])
+    with torch.no_grad():
+        got = net.predictor(x.to(DEV)).cpu()
+    torch.cuda.synchronize()
+    res = {"samples": {}, "upper": {}, "finite": {}, "out_finite": bool(torch.isfinite(got).all())}
+    for b in (range(B) if samples is None else samples):
+        hl = PredictorLayers(net.predictor, b)
+        e = O.predictor_forward_emu(sd, x[b:b + 1], taps=hl, force=hl)
+        hl.out["out"] = metrics(got[b:b + 1], e)
+        res["samples"][b] = hl.out
+        res["upper"].update({k: max(v, res["upper"].get(k, 0.0)) for k, v in hl.upper.items()})
+        res["finite"].update({k: v and res["finite"].get(k, True) for k, v in hl.finite.items()})
+    return res, got, x
 
 
 def sampler_step_case(seed=0):

@@ -96,7 +96,7 @@ def test_conv_persistent(args):
     # B, H, W, c0, c1, cout, mode, gn, silu, residual, persist_grid
     (2, 24, 40, 64, 0, 256, 0, True, True, False, 0),       # two row-of-256 units per tile, ragged last tile, GroupNorm fold (all nine border classes)
     (3, 18, 18, 128, 64, 512, 0, True, True, False, 0),     # cat input, two row tiles, tiles spanning samples (400 positions per sample)
-    (5, 10, 12, 64, 0, 256, 0, True, False, False, 3),      # 3 workgroups: whole units + a stream-K remainder cut across workgroups, several samples per tile
+    (5, 10, 12, 64, 0, 256, 0, True, False, False, 3),      # 3 workgroups: ranges of whole units, several samples per tile (3 units for kind 1, 6 for kind 2: no remainder)
     (2, 36, 36, 256, 0, 512, 0, True, True, True, 7),       # residual; 7 workgroups: units cut into three parts (finish kernel sums in workgroup order)
     (2, 16, 24, 128, 0, 256, 2, False, False, False, 0),    # Upsample: four parity classes of 2 x 2 taps
     (3, 9, 9, 256, 0, 512, 2, False, False, False, 5),      # Upsample, stream-K across parity classes and row tiles
@@ -299,10 +299,67 @@ def test_attention(shape, flash):
     assert not m["nan"] and m["rel_rms_branch"] < 1.2e-2, m
 
 
-@pytest.mark.parametrize("shape", [(2, 64, 96), (1, 256, 256), (1, 40, 72)])
+@pytest.mark.parametrize("shape", [(2, 64, 96), (1, 256, 256), (1, 40, 72), (1, 33, 33)])
 def test_predictor(shape):
     m = C.predictor_case(*shape)
+    print(shape, m)
     assert not m["nan"] and m["rel_rms"] < 1.5e-2, m
+    assert m["tile_max"] < C.PRED_TILE_TOL and m["elem_max"] < C.PRED_ELEM_TOL, m     # no 3-channel x 32 x 32 block far off
+
+
+@pytest.mark.parametrize("args", [
+    # B, H, W, c0, cout, ksize, convsk, persist_grid, skmix, expected key
+    (2, 20, 20, 64, 64, 3, 0, 0, -1, 20),          # conv3x3_halo, TM = 64, ragged tiles
+    (5, 128, 128, 64, 128, 3, 0, 0, -1, 120),      # conv3x3_halo, TM = 128 (>= 256 workgroups, no split)
+    (1, 18, 18, 512, 512, 3, 0, 0, -1, 20),        # split-K: 16 workgroups x 32 chunks, the finish kernel applies the activation after the sum
+                                                   # (that it splits is asserted below: the same launch with split-K off differs)
+    (3, 64, 80, 64, 64, 3, 0, 7, -1, 23),          # conv_ws, persistent ranges crossing samples (grid forced to 7)
+    (2, 24, 40, 64, 256, 3, 1, 0, 0, 125),         # conv_sk kind 1 (persistent 8-wave): 9 units of 2 chunks on 18 workgroups - EVERY unit is cut and
+                                                   # summed by the finish kernel, which applies the activation (the shared sk_epilogue)
+    (5, 12, 18, 64, 256, 3, 1, 3, 0, 125),         # ... 5 units on 3 workgroups: 3 whole units (the kernel's own epilogue) + a remainder of 2 units
+                                                   # cut across the 3 workgroups (finish kernel)
+    (2, 24, 40, 64, 256, 3, 2, 0, 0, 127),         # conv_sk kind 2 (one-shot 4-wave)
+    (2, 36, 36, 256, 512, 3, 2, 7, 0, 127),        # ... units cut into three parts on 7 workgroups
+    (2, 24, 40, 64, 256, 3, 2, 0, 1, 129),         # the mixed wide + short schedule
+    (2, 24, 40, 64, 64, 1, -1, 0, -1, 0),          # cgemm 1x1, TM = 64
+    (2, 24, 40, 64, 128, 1, -1, 0, -1, 100),       # cgemm 1x1, TM = 128
+], ids=["halo64", "halo128", "splitk", "conv_ws_ranges", "sk8_all_cut", "sk8_whole_and_remainder", "sk4", "sk4_streamk", "skmix", "cgemm64", "cgemm128"])
+def test_conv_leaky_relu_epilogue(args):
+    """The predictor's LeakyReLU(0.2) epilogue (act = 2) of every conv kernel family against torch.  The reference has 30-70 % negative
+    pre-activations, so a wrong slope moves a large share of the outputs."""
+    B, H, W, c0, cout, ksize, convsk, grid, skmix, key = args
+    L = C.ulib.load()
+    C.ulib.check(L.ucdir_debug_flag(b"convsk", convsk))
+    C.ulib.check(L.ucdir_debug_flag(b"persist_grid", grid))
+    C.ulib.check(L.ucdir_debug_flag(b"skmix", skmix))
+    try:
+        (m, keys) = _profile_keys(L, lambda: C.conv_case(B, H, W, c0, 0, cout, ksize, 0, False, 2, False, seed=9))
+        m2 = C.conv_case(B, H, W, c0, 0, cout, ksize, 0, False, 2, False, seed=9)
+    finally:
+        C.ulib.check(L.ucdir_debug_flag(b"skmix", -1))
+        C.ulib.check(L.ucdir_debug_flag(b"persist_grid", 0))
+        C.ulib.check(L.ucdir_debug_flag(b"convsk", -1))
+    print(args, keys, m)
+    assert keys.keys() == {key}, keys
+    assert 0.3 < m["neg_frac"] < 0.7, m
+    assert not m["nan"] and m["rel_rms"] < OP_TOL, m
+    assert m["stats_rel"] < 1e-3, m
+    assert m2["rel_rms"] == m["rel_rms"] and m2["max_abs"] == m["max_abs"], (m, m2)     # run to run
+    _tile_ok(m)
+    if args[:6] == (1, 18, 18, 512, 512, 3):
+        # the key is the same with and without split-K: pin the split by its summation order.  With split-K off the one-shot launch
+        # sums K in another order, so the output (and its error) must differ - and still meet the bounds
+        C.ulib.check(L.ucdir_debug_flag(b"convsk", 0))
+        C.ulib.check(L.ucdir_debug_flag(b"splitk", 0))
+        try:
+            (m3, keys3) = _profile_keys(L, lambda: C.conv_case(B, H, W, c0, 0, cout, ksize, 0, False, 2, False, seed=9))
+        finally:
+            C.ulib.check(L.ucdir_debug_flag(b"splitk", -1))
+            C.ulib.check(L.ucdir_debug_flag(b"convsk", -1))
+        assert keys3.keys() == {key}, keys3
+        assert (m3["rel_rms"], m3["max_abs"]) != (m["rel_rms"], m["max_abs"]), (m, m3)
+        assert not m3["nan"] and m3["rel_rms"] < OP_TOL, m3
+        _tile_ok(m3)
 
 
 def test_sampler_step_exact():

@@ -2207,9 +2207,12 @@ static void predictor_finalize(ucdir_predictor* c) {
 }
 
 static void predictor_plan(ucdir_predictor* c, int B, int H, int W) {
+    // checked before any state changes: a rejected shape must leave the last plan intact (ucdir_predictor_forward compares
+    // against c->B / H / W, so a half-applied plan would make the next call with the same shape skip re-planning)
+    require(B >= 1, "predictor: B must be >= 1");
+    require(H >= 33 && W >= 33, "predictor: H, W must be >= 33 (reflect pad)");
     c->apool.release(); c->act.clear();
     c->B = B; c->H = H; c->W = W; c->Hc = (H / 32 + 1) * 32; c->Wc = (W / 32 + 1) * 32;
-    require(H >= 33 && W >= 33, "predictor: H, W must be >= 33 (reflect pad)");
     const int ch[5] = {64, 64, 128, 256, 512};
     for (int l = 0; l < 5; ++l) {
         const int h = c->Hc >> l, w = c->Wc >> l;
@@ -2321,6 +2324,33 @@ int32_t ucdir_predictor_finalize(ucdir_predictor* p) {
     DevGuard dg(p->device);
     predictor_finalize(p);
     HIPC(hipDeviceSynchronize());
+    API_END
+}
+
+// reference module name -> the engine's activation: conv{l}_1 -> a{l}, conv{l}_2 -> c{l}, pool{l} -> p{l}, upv{l} -> u{l}
+static const Act& predictor_act(ucdir_predictor* c, const std::string& name) {
+    std::string key;
+    if (name.size() == 7 && name.compare(0, 4, "conv") == 0 && name[4] >= '1' && name[4] <= '9' && name[5] == '_' && (name[6] == '1' || name[6] == '2'))
+        key = std::string(1, name[6] == '1' ? 'a' : 'c') + name[4];
+    else if (name.size() == 5 && name.compare(0, 4, "pool") == 0 && name[4] >= '1' && name[4] <= '4')
+        key = std::string("p") + name[4];
+    else if (name.size() == 4 && name.compare(0, 3, "upv") == 0 && name[3] >= '6' && name[3] <= '9')
+        key = std::string("u") + name[3];
+    require(!key.empty(), "unknown predictor activation " + name);
+    auto it = c->act.find(key);
+    require(it != c->act.end(), "predictor: no forward has run at this shape");
+    return it->second;
+}
+
+int32_t ucdir_predictor_debug_read(ucdir_predictor* p, const char* name, float* dst, int64_t dst_elems, void* stream) {
+    API_BEGIN
+    require(p && name && dst, "null argument");
+    DevGuard dg(p->device);
+    const Act& a = predictor_act(p, name);
+    const int64_t n = (int64_t)a.B * a.C * a.H * a.W;
+    require(n == dst_elems, "predictor_debug_read: dst has " + std::to_string(dst_elems) + " elements, activation has " + std::to_string(n));
+    hipLaunchKernelGGL(act_to_nchw_kernel, dim3(2048), dim3(256), 0, (hipStream_t)stream, a.p, dst, a.B, a.C, a.H, a.W);
+    HIPC(hipGetLastError());
     API_END
 }
 

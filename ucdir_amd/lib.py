@@ -65,6 +65,7 @@ _SIGS = {
     "ucdir_predictor_load_weight": (c_int32, [c_void_p, c_char_p, c_void_p, POINTER(c_int64), c_int32]),
     "ucdir_predictor_finalize": (c_int32, [c_void_p]),
     "ucdir_predictor_forward": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "ucdir_predictor_debug_read": (c_int32, [c_void_p, c_char_p, c_void_p, c_int64, c_void_p]),
     "ucdir_op_conv": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                 c_void_p]),

@@ -479,7 +479,31 @@ class UNetSeeInDark(nn.Module):
         B, _, H, W = x.shape
         y = torch.empty_like(x)
         _lib.check(L.ucdir_predictor_forward(self._handle(), _ptr(x), _ptr(y), B, H, W, _stream_ptr(x.device)))
+        self._last_shape = (B, H, W)
         return y
+
+    def debug_read(self, name):
+        """Activation ``name`` of the last forward (reference module names: conv{l}_1 / conv{l}_2 after LeakyReLU, pool{l},
+        upv{l}) as (B, C, Hc >> l, Wc >> l) fp32 on the padded grid (tests).  C is the carried count: 64 for the 32-channel
+        layers, whose upper half is zero."""
+        import re
+        m = re.fullmatch(r"conv([1-9])_[12]|pool([1-4])|upv([6-9])", name)
+        if m is None or getattr(self, "_last_shape", None) is None:
+            raise KeyError(name)
+        B, H, W = self._last_shape
+        Hc, Wc = (H // 32 + 1) * 32, (W // 32 + 1) * 32
+        if m.group(1):
+            lvl = int(m.group(1)) - 1 if int(m.group(1)) <= 5 else 9 - int(m.group(1))
+            ch = lvl
+        elif m.group(2):
+            lvl = int(m.group(2))
+            ch = lvl - 1                      # max pooling keeps the channels of the level above
+        else:
+            lvl = ch = 9 - int(m.group(3))
+        out = torch.empty(B, max(64, 32 << ch), Hc >> lvl, Wc >> lvl, device=next(self.parameters()).device)
+        _lib.check(_lib.load().ucdir_predictor_debug_read(self._handle(), name.encode(), _ptr(out), out.numel(),
+                                                          _stream_ptr(out.device)))
+        return out
 
     def __del__(self):
         try:
