@@ -152,6 +152,20 @@ int32_t ucdir_fewstep_update_batched(float* x, const float* eps, float* m_prev, 
 int32_t ucdir_gather_windows(const float* x, int32_t B, int32_t C, int32_t H, int32_t W, int32_t pad, const int32_t* win_dev,
                              int32_t nwin, int32_t skip, float* out, void* stream);
 
+/* Full-reference scores of the val loop (metrics.calculate_psnr / calculate_ssim on the uint8 images of tensor2img_u8_device).
+ * a (restored) and b (target): fp32 (B, C, H, W) in [-1, 1], C = 1 or 3, element strides per image (_sn), channel (_sc) and row
+ * (_sh), column stride 1 (a cropped view such as DDPM.SR's is read in place).  Per (image, channel), index n * C + c:
+ *   sse[]      = sum of (qa - qb)^2 over the H x W uint8 pixels, exact;
+ *   ssim_sum[] = sum of the SSIM map (11-tap sigma-1.5 Gaussian, fp64) over the valid region [5, H-5) x [5, W-5); NaN when H or
+ *                W is below 11.
+ * workspace: device buffer of ucdir_image_metrics_workspace_bytes(B, C, H, W) bytes (-1 on a bad shape), 8-byte aligned, like
+ * sse and ssim_sum.  No atomics: the results are bit-identical from run to run. */
+int64_t ucdir_image_metrics_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W);
+int32_t ucdir_image_metrics(const float* a, int64_t a_sn, int64_t a_sc, int64_t a_sh,
+                            const float* b, int64_t b_sn, int64_t b_sc, int64_t b_sh,
+                            int32_t B, int32_t C, int32_t H, int32_t W,
+                            void* workspace, uint64_t* sse, double* ssim_sum, void* stream);
+
 /* ---- introspection (tests / profiling) ---------------------------------------------------
  * Copy the activation a layer produced in the last forward into dst as (B,C,Hc,Wc) fp32 NCHW
  * (Hc, Wc = compute size).  layer = state_dict prefix ("downs.0", "ups.7", "mid.0", ...),

@@ -67,6 +67,8 @@ def make_parser():
     parser.add_argument("--sampler-steps", type=int, default=None, help="network calls of a ddim / dpm_solver++ restoration")
     parser.add_argument("--sampler-order", type=int, choices=[1, 2], default=None, help="dpm_solver++ multistep order")
     parser.add_argument("--ddim-eta", type=float, default=None, help="ddim noise scale (0: deterministic, 1: the reference's setting)")
+    parser.add_argument("--metrics-device", choices=["cpu", "gpu"], default="cpu",
+                        help="score PSNR / SSIM on the host (numpy / scipy) or on the GPU (HIP kernel, the same uint8 images)")
     return parser
 
 
@@ -139,6 +141,7 @@ def main(argv=None):
         if group[0][2] and rank != 0:
             return                                                # sharded image: every rank holds the same result; rank 0 reports it
         name = opt["name"]
+        dev_scores = diffusion.current_metrics() if args.metrics_device == "gpu" else None
         for j, (i, _, _) in enumerate(group):
             fname = os.path.splitext(os.path.basename(val_set.sr_path[i]))[0]
             vis = diffusion.visuals_u8(j)
@@ -147,8 +150,12 @@ def main(argv=None):
             Metrics.save_jpg(hr_img, "{}/{}_{}_hr.png".format(result_path, fname, name))
             Metrics.save_jpg(lr_img, "{}/{}_{}_lr.png".format(result_path, fname, name))
             Metrics.save_jpg(fake_img, "{}/{}_{}_inf.png".format(result_path, fname, name))
-            tot_psnr += Metrics.calculate_psnr(sr_img, hr_img)
-            tot_ssim += Metrics.calculate_ssim(sr_img, hr_img)
+            if dev_scores is not None:
+                tot_psnr += dev_scores[0][j]
+                tot_ssim += dev_scores[1][j]
+            else:
+                tot_psnr += Metrics.calculate_psnr(sr_img, hr_img)
+                tot_ssim += Metrics.calculate_ssim(sr_img, hr_img)
             n += 1
             logger.info("val index %d" % i)
 

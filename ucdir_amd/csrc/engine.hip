@@ -30,6 +30,7 @@
 #include "common.h"
 #include "misc.hip.h"
 #include "fewstep.hip.h"
+#include "image_metrics.hip.h"
 #include "pack.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -1836,6 +1837,67 @@ int32_t ucdir_gather_windows(const float* x, int32_t B, int32_t C, int32_t H, in
     const int xblocks = (skip + 255) / 256;
     hipLaunchKernelGGL(gather_windows_kernel, dim3((unsigned)(xblocks * skip), (unsigned)C, (unsigned)(nwin * B)), dim3(256), 0, (hipStream_t)stream,
                        x, B, C, H, W, pad, win_dev, skip, out);
+    HIPC(hipGetLastError());
+    API_END
+}
+
+// val-loop scores (csrc/image_metrics.hip.h): tiles of IM_TW x IM_TR valid-region outputs; at least one tile per (image, channel)
+// so that the SSE of images below 11 x 11 is still counted
+static void image_metrics_grid(int32_t H, int32_t W, int& nx, int& ny) {
+    const int hg = H > 10 ? H - 10 : 1, wg = W > 10 ? W - 10 : 1;
+    nx = (wg + IM_TW - 1) / IM_TW;
+    ny = (hg + IM_TR - 1) / IM_TR;
+}
+
+int64_t ucdir_image_metrics_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W) {
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return -1;
+    int nx, ny;
+    image_metrics_grid(H, W, nx, ny);
+    return (int64_t)B * C * nx * ny * (int64_t)(sizeof(double) + sizeof(unsigned long long));
+}
+
+int32_t ucdir_image_metrics(const float* a, int64_t a_sn, int64_t a_sc, int64_t a_sh, const float* b, int64_t b_sn, int64_t b_sc,
+                            int64_t b_sh, int32_t B, int32_t C, int32_t H, int32_t W, void* workspace, uint64_t* sse, double* ssim_sum,
+                            void* stream) {
+    API_BEGIN
+    const std::string w("ucdir_image_metrics");
+    require(a && b && workspace && sse && ssim_sum, w + ": null argument");
+    require(B > 0 && H > 0 && W > 0, w + ": bad shape");
+    require(C == 1 || C == 3, w + ": C must be 1 or 3");
+    require((int64_t)B * C <= 65535, w + ": more than 65535 (image, channel) pairs");
+    require(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)sse & 7) == 0 && ((uintptr_t)ssim_sum & 7) == 0,
+            w + ": workspace and outputs must be 8-byte aligned");
+    hipPointerAttribute_t pa;
+    HIPC(hipPointerGetAttributes(&pa, a));
+    require(pa.type == hipMemoryTypeDevice, w + ": a is not a device pointer");
+    const void* others[4] = {b, workspace, sse, ssim_sum};
+    const char* names[4] = {"b", "workspace", "sse", "ssim_sum"};
+    for (int i = 0; i < 4; ++i) {
+        hipPointerAttribute_t po;
+        HIPC(hipPointerGetAttributes(&po, others[i]));
+        require(po.type == hipMemoryTypeDevice && po.device == pa.device, w + ": " + names[i] + " must live on the device of a");
+    }
+    int nx, ny;
+    image_metrics_grid(H, W, nx, ny);
+    const long long ntiles = (long long)nx * ny;
+    require(ntiles <= 0x7fffffffLL, w + ": image too large");
+    // the 11-tap Gaussian of metrics._ssim, normalised with numpy's summation order for 11 float64 values
+    ImageMetricsTaps taps;
+    for (int k = 0; k < 11; ++k) taps.w[k] = std::exp(-(double)((k - 5) * (k - 5)) / (2 * 1.5 * 1.5));
+    double tot = ((taps.w[0] + taps.w[1]) + (taps.w[2] + taps.w[3])) + ((taps.w[4] + taps.w[5]) + (taps.w[6] + taps.w[7]));
+    tot += taps.w[8];
+    tot += taps.w[9];
+    tot += taps.w[10];
+    for (int k = 0; k < 11; ++k) taps.w[k] /= tot;
+    DevGuard dg(pa.device);
+    double* part_ssim = (double*)workspace;
+    unsigned long long* part_sse = (unsigned long long*)(part_ssim + (long long)B * C * ntiles);
+    hipLaunchKernelGGL(image_metrics_tile_kernel, dim3((unsigned)ntiles, (unsigned)(B * C)), dim3(256), 0, (hipStream_t)stream,
+                       a, (long long)a_sn, (long long)a_sc, (long long)a_sh, b, (long long)b_sn, (long long)b_sc, (long long)b_sh,
+                       C, H, W, nx, ny, taps, part_ssim, part_sse);
+    HIPC(hipGetLastError());
+    hipLaunchKernelGGL(image_metrics_finish_kernel, dim3((unsigned)(B * C)), dim3(256), 0, (hipStream_t)stream, part_ssim, part_sse,
+                       (int)ntiles, (int)(H > 10 && W > 10), (unsigned long long*)sse, ssim_sum);
     HIPC(hipGetLastError());
     API_END
 }

@@ -76,3 +76,33 @@ def calculate_ssim(img1, img2):
     if img1.ndim == 2:
         return _ssim(img1, img2)
     return float(np.mean([_ssim(img1[..., c], img2[..., c]) for c in range(img1.shape[2])]))
+
+
+def psnr_ssim_device(sr, hr):
+    """calculate_psnr / calculate_ssim of the uint8 images tensor2img_u8_device makes of ``sr`` and ``hr``, scored on the GPU
+    (csrc/image_metrics.hip.h) without moving the images: (B, C, H, W) or (C, H, W) CUDA tensors in [-1, 1] -> (psnr list, ssim
+    list), one value per image.  One device-to-host copy of the (image, channel) sums.  PSNR is bit-equal to the host formula (the
+    numpy sum of integer-valued float64 is exact, and so is the kernel's integer SSE); SSIM is the same fp64 map summed in another
+    order, and NaN when H or W is below 11 like numpy's mean of an empty map."""
+    import torch
+    from .ucdir import image_metrics_
+    if sr.dim() == 3:
+        sr, hr = sr.unsqueeze(0), hr.unsqueeze(0)
+    if sr.dim() != 4:
+        raise ValueError("psnr_ssim_device takes (B, C, H, W) or (C, H, W) tensors")
+    B, C, H, W = sr.shape
+    out = torch.empty(2 * B * C, dtype=torch.int64, device=sr.device if sr.is_cuda else "cpu")
+    image_metrics_(sr, hr, out=out)
+    host = out.cpu()                                # the only synchronisation: sse and ssim_sum share this buffer
+    sse_h = host[:B * C].tolist()
+    ssim_h = host[B * C:].view(torch.float64).tolist()
+    psnr, ssim = [], []
+    for n in range(B):
+        mse = sum(sse_h[n * C:(n + 1) * C]) / (C * H * W)
+        psnr.append(float("inf") if mse == 0 else 20 * math.log10(255.0 / math.sqrt(mse)))
+        if H < 11 or W < 11:
+            ssim.append(float("nan"))
+        else:
+            ssim.append(float(np.mean([ssim_h[n * C + c] / ((H - 10) * (W - 10)) for c in range(C)])))
+    return psnr, ssim
+

@@ -109,6 +109,14 @@ class DDPM:
         out["INF"] = cv(pre[j, :, 64:-64, 64:-64]) if pre is not None else cv(self.data["SR"][j])
         return out
 
+    def current_metrics(self):
+        """(psnr list, ssim list) of the images of the last ``test()``: the final SR block against data["HR"], scored on the GPU
+        (metrics.psnr_ssim_device) with the same uint8 quantisation as ``visuals_u8``; one device-to-host copy."""
+        from .metrics import psnr_ssim_device
+        B = self.data["SR"].shape[0]
+        sr = self.SR[self.SR.shape[0] - B:] if self.SR.dim() == 4 else self.SR
+        return psnr_ssim_device(sr, self.data["HR"])
+
     def load_network(self):
         """model/model.py:224-251: in val phase with EMA on, ``{prefix}_gen_ema.pth`` is loaded strict=False."""
         prefix = self.opt["path"]["resume_state"]

@@ -386,6 +386,33 @@ def gather_windows(x, pad, win_dev, skip):
     return out
 
 
+def image_metrics_(a, b, out=None):
+    """Val-loop scores of restored images ``a`` against targets ``b`` (csrc/image_metrics.hip.h), fp32 (B, C, H, W) CUDA tensors in
+    [-1, 1], C = 1 or 3, unit column stride (cropped views are read in place).  Per (image, channel), on the device:
+    ``sse`` (B, C) = the exact sum of squared uint8 differences (int64), ``ssim_sum`` (B, C) = the SSIM map summed over the valid
+    region (float64, NaN below 11 x 11).  Both are views of ONE buffer of 2 B C int64 (``out`` when given, on the device of ``a``),
+    so a single copy brings them to the host."""
+    if a.dim() != 4 or tuple(a.shape) != tuple(b.shape):
+        raise _lib.UcdirError(f"image_metrics_: a and b must be (B, C, H, W) of one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+    B, C, H, W = a.shape
+    if C not in (1, 3):
+        raise _lib.UcdirError(f"image_metrics_: C must be 1 or 3, got {C}")
+    if a.stride(3) != 1 or b.stride(3) != 1:
+        raise _lib.UcdirError("image_metrics_: the column stride of a and b must be 1")
+    if not (a.is_cuda and b.is_cuda and a.device == b.device and a.dtype == torch.float32 and b.dtype == torch.float32):
+        raise _lib.UcdirError("image_metrics_ needs fp32 CUDA tensors on one device")
+    L = _lib.load()
+    ws = torch.empty(L.ucdir_image_metrics_workspace_bytes(B, C, H, W) // 8, dtype=torch.int64, device=a.device)
+    if out is None:
+        out = torch.empty(2 * B * C, dtype=torch.int64, device=a.device)
+    elif not (out.device == a.device and out.dtype == torch.int64 and out.is_contiguous() and out.numel() == 2 * B * C):
+        raise _lib.UcdirError("image_metrics_: out must be a contiguous int64 tensor of 2 B C elements on the device of a")
+    sse, ssim_sum = out[:B * C].view(B, C), out[B * C:].view(torch.float64).view(B, C)
+    _lib.check(L.ucdir_image_metrics(_ptr(a), a.stride(0), a.stride(1), a.stride(2), _ptr(b), b.stride(0), b.stride(1), b.stride(2),
+                                     B, C, H, W, _ptr(ws), _ptr(sse), _ptr(ssim_sum), _stream_ptr(a.device)))
+    return sse, ssim_sum
+
+
 def fill_normal_(x, seed, step=0, seeds=None):
     """x <- N(0, 1) from the sampler's counter-based generator (x_T = step 0 of the stream the update kernel draws from);
     ``seeds``: per-sample streams as in ``sampler_step_rng_``."""
