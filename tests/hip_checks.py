@@ -29,14 +29,17 @@ DEV = "cuda"
 
 EMU_LAYER_TOL = 2e-3   # one layer of the HIP path against the oracle's bf16-emulation mode ON THE SAME INPUTS (teacher forcing): what is left is
                        # fp32 summation order and single bf16 rounding flips.  Measured (tools/_emu_probe.py): worst layer 6.7e-4 (full SID, B = 1),
-                       # 4.4e-4 (B = 4), 8.9e-4 (small configuration) - the attention blocks of the 18^2 / 36^2 levels; everything else <= 4e-4
+                       # 4.4e-4 (B = 4), 8.9e-4 (small configuration) - the attention blocks of the 18^2 / 36^2 levels; everything else <= 4e-4.
+                       # The val shapes (tests/test_val_shapes_gpu.py: 416^2, non-square, akgm_ws64's limits, 416 x 1664): worst 5.90e-4
+                       # (mid.0, B = 1 at 416^2)
 TILE = (64, 32, 32)    # (channels, rows, columns) of one tile_max block; one sample per block
 # tile-local bounds (metrics() keys tile_max / elem_max) and the attention-vs-emulation bounds: each about 1.5x the worst value
 # measured on the MI355X over every case that asserts it; tests/test_tile_metric_cpu.py shows the modelled faults exceed them
 OP_TILE_TOL = 4e-3     # single operator vs torch: worst 2.61e-3 (test_conv_stream_k_with_res_conv[level4_ksplit], the res_conv output)
 OP_ELEM_TOL = 5.5e-2   # ... worst 3.65e-2 (test_akgm_block_kernel_at_narrow_groups[cg8_th8]): one bf16 step of a large output
 EMU_TILE_TOL = 1.3e-3  # one layer vs the emulation: worst 8.84e-4 (full SID B = 1, an attention block at 36^2); B = 32: 6.3e-4,
-                       # 1024^2 windows: 4.3e-4, fp16 attention windows: 4.2e-4 (tests/test_layerwise_gpu.py)
+                       # 1024^2 windows: 4.3e-4, fp16 attention windows: 4.2e-4 (tests/test_layerwise_gpu.py); the val shapes: 6.34e-4
+                       # (ups.5, B = 4 at 288 x 800), while a layer with its last 32 columns one row down (shift_last_strip) gives >= 1.41
 EMU_ELEM_TOL = 6.5e-2  # ... one element (asserted by tests/test_predictor_gpu.py): worst 4.19e-2 (conv8_2, B = 16 at 384^2); the predictor's
                        # layers against its emulation: rel-RMS <= 1.04e-4, tile_max <= 3.46e-4 (all shapes; no GroupNorm to amplify rounding)
 PRED_TILE_TOL = 1e-2   # the whole predictor vs the fp32 oracle (test_predictor, 3 channels x 32 x 32 blocks): worst 6.79e-3 (B = 2, 64 x 96)
@@ -350,11 +353,14 @@ class HipLayers:
     """One sample of the last HIP forward, layer by layer, for oracle.dy3h_naive_forward_emu without holding the network on the
     host: as ``force`` it reads a stored activation (debug_read, sliced to the sample on the device) when the emulation asks
     for it; as ``taps`` it compares the emulated layer output (bf16-rounded, like the stored one) with it and keeps only the
-    metrics (``self.out``).  No other forward may run on the network while it is in use: debug_read reads the last one."""
+    metrics (``self.out``).  No other forward may run on the network while it is in use: debug_read reads the last one.
+    ``controls``: {layer or layer:h1: fn}; the emulated output of each such layer is also compared with fn(stored activation),
+    a deliberately wrong host-side copy (``self.controls_out``), while the emulation still continues from the stored one."""
 
-    def __init__(self, dn, b, prefix="denoise_fn."):
+    def __init__(self, dn, b, prefix="denoise_fn.", controls=None):
         from ucdir_amd.spec import unet_layers
         self.dn, self.b, self.out, self._last = dn, b, {}, (None, None)
+        self.controls, self.controls_out = dict(controls or {}), {}
         self.names = {}
         for Ld in unet_layers(dn.cfg):
             self.names[prefix + Ld.name] = (Ld.name, Ld.name, "out")
@@ -374,20 +380,70 @@ class HipLayers:
 
     def __setitem__(self, key, y):
         if key in self.names:
-            self.out[self.names[key][0]] = metrics(self[key], bfr(y))
+            name = self.names[key][0]
+            self.out[name] = metrics(self[key], bfr(y))
+            if name in self.controls:
+                self.controls_out[name] = metrics(self.controls[name](self[key]), bfr(y))
 
 
-def layerwise_emu_sample(dn, sd, x6, lvl, guide, b, pad, attn_dtype="bf16"):
+def layerwise_emu_sample(dn, sd, x6, lvl, guide, b, pad, attn_dtype="bf16", controls=None):
     """Layer-wise metrics of sample ``b`` of the LAST forward of ``dn`` (x6, lvl, guide: that forward's host inputs; ``pad``:
     the forward reflect-padded them by pad32 like forward_split, else they are already multiples of 32) against the emulation
-    fed with the HIP path's own activations.  Returns {layer or layer:h1: metrics}."""
+    fed with the HIP path's own activations.  Returns {layer or layer:h1: metrics}; with ``controls`` (HipLayers) the pair
+    ({layer: metrics}, {controlled layer: metrics of the wrong copy})."""
     xs, gs = x6[b:b + 1], guide[b:b + 1]
     if pad:
         ph, pw = O.pad32(x6.shape[-2]), O.pad32(x6.shape[-1])
         xs, gs = F.pad(xs, (0, pw, 0, ph), mode="reflect"), F.pad(gs, (0, pw, 0, ph), mode="reflect")
-    hl = HipLayers(dn, b)
+    hl = HipLayers(dn, b, controls=controls)
     O.dy3h_naive_forward_emu(sd, xs, lvl[b:b + 1], gs, taps=hl, force=hl, attn_dtype=attn_dtype)
-    return hl.out
+    return (hl.out, hl.controls_out) if controls is not None else hl.out
+
+
+def shift_last_strip(t, cols=TILE[2]):
+    """Negative control: a copy of activation ``t`` (..., H, W) whose last ``cols`` columns are shifted down by one row (row r
+    holds row r - 1; row 0 is kept), as a kernel that mixed up a strip's row offset would store it.  Host-side only."""
+    y = t.clone()
+    c = min(cols, t.shape[-1])
+    y[..., 1:, -c:] = t[..., :-1, -c:]
+    return y
+
+
+AKGM_KEYS = (110, 111, 112, 113, 114, 115, 116)   # profiler keys of the AKGM launch of a residual block (one per block and forward)
+
+
+def ws64_tile(B, H, W, ncu):
+    """Python copy of the engine's akgm_ws64 dispatch rule (engine.hip, run_akgm_halo) for a C = 512 AKGM plane of H x W at
+    batch B on a device of ``ncu`` compute units: the tile size the persistent kernel takes (128 | 64 positions; key 116), or
+    0 for the one-shot akgm_halo_stage_kernel (key 111).  A tile's halo, 32 npt + 2 (W + 2) + 2 positions, must fit the 272
+    of AkWs64::HPOS; 128-position tiles engage from four per tile range, 64-position ones when a range holds 1.5 halos."""
+    if H < 2 or (H + 2) * (W + 2) >= 32768:
+        return 0
+    nrole = 16                                   # 128 / AkWs64::NW
+    nslots = max(ncu // nrole * nrole, nrole) // nrole
+    span = (H - 1) * (W + 2) + W
+    for npt in (4, 2):
+        hpos = 32 * npt + 2 * (W + 2) + 2
+        if hpos > 272:
+            continue
+        tps = -(-span // (32 * npt))
+        enough = B * tps >= 4 * nslots if npt == 4 else 2 * B * span >= 3 * nslots * hpos
+        if enough:
+            return 32 * npt
+    return 0
+
+
+def ws64_prediction(cfg, B, Hc, Wc, ncu):
+    """{level: (H, W, tile, blocks)} for every level whose residual blocks run AKGM at C = 512 (ws64_tile's choice), on a
+    forward of compute size Hc x Wc."""
+    from ucdir_amd.spec import unet_layers
+    out = {}
+    for Ld in unet_layers(cfg):
+        if Ld.kind == "block" and Ld.cout == 512:
+            h, w = Hc >> Ld.level, Wc >> Ld.level
+            _, _, t, n = out.get(Ld.level, (h, w, ws64_tile(B, h, w, ncu), 0))
+            out[Ld.level] = (h, w, t, n + 1)
+    return out
 
 
 def build_net(cfg: UNetConfig, seed=0):
@@ -522,6 +578,22 @@ def predictor_case(B, H, W, seed=3, net_sd=None):
 # the predictor's activations in forward order, by the reference's module names (UNetSeeInDark.debug_read)
 PREDICTOR_LAYERS = (["conv1_1", "conv1_2", "pool1"] + [n for l in range(2, 5) for n in (f"conv{l}_1", f"conv{l}_2", f"pool{l}")]
                     + ["conv5_1", "conv5_2"] + [n for l in range(6, 10) for n in (f"upv{l}", f"conv{l}_1", f"conv{l}_2")])
+
+
+def assert_layers_ok(outs, keys, what):
+    """Print and assert the per-layer bounds of a whole-network layer-wise check.  outs: {sample: {activation: metrics}} as
+    layerwise_emu_sample returns them for the full SID configuration; keys: the forward's profiler keys."""
+    for b, out in outs.items():
+        worst = max(out, key=lambda k: out[k]["rel_rms"])
+        worst_t = max(out, key=lambda k: out[k]["tile_max"])
+        print(f"{what}, sample {b}: {len(out)} activations, worst {worst}: {out[worst]['rel_rms']:.3e}, "
+              f"worst tile {worst_t}: {out[worst_t]['tile_max']:.3e} at {out[worst_t]['tile_at']}")
+    print(f"{what}: profiler keys {sorted(keys)}")
+    for b, out in outs.items():
+        assert len(out) == 36 + 27, len(out)    # 36 layer outputs (stem, 27 blocks, 4 + 4 resamplers) + 27 h1 tensors
+        for k, m in out.items():
+            assert not m["nan"] and m["rel_rms"] < EMU_LAYER_TOL, (b, k, m)
+            assert m["tile_max"] < EMU_TILE_TOL, (b, k, m)
 
 
 def emu_layer_ok(m):

@@ -78,19 +78,7 @@ def test_attention_masking_of_the_last_key_and_query(shape, mode):
 
 
 # ---- the network layer by layer ----------------------------------------------------------------------------------------------
-def _layers_ok(outs, keys, what):
-    """outs: {sample: {activation: metrics}}."""
-    for b, out in outs.items():
-        worst = max(out, key=lambda k: out[k]["rel_rms"])
-        worst_t = max(out, key=lambda k: out[k]["tile_max"])
-        print(f"{what}, sample {b}: {len(out)} activations, worst {worst}: {out[worst]['rel_rms']:.3e}, "
-              f"worst tile {worst_t}: {out[worst_t]['tile_max']:.3e} at {out[worst_t]['tile_at']}")
-    print(f"{what}: profiler keys {sorted(keys)}")
-    for b, out in outs.items():
-        assert len(out) == 36 + 27, len(out)    # 36 layer outputs (stem, 27 blocks, 4 + 4 resamplers) + 27 h1 tensors
-        for k, m in out.items():
-            assert not m["nan"] and m["rel_rms"] < C.EMU_LAYER_TOL, (b, k, m)
-            assert m["tile_max"] < C.EMU_TILE_TOL, (b, k, m)
+_layers_ok = C.assert_layers_ok
 
 
 def _forward(net, x6, lvl, guide, naive):

@@ -179,3 +179,35 @@ def test_tile_metric_ragged_blocks_and_determinism():
     rms = float(ref.pow(2).mean().sqrt())
     assert m["tile_at"] == (1, 64, 32, 32) and abs(m["tile_max"] - 1.0 / math.sqrt(48) / rms) < 1e-6, m
     assert abs(m["elem_max"] - 1.0 / rms) < 1e-6 and m == C.metrics(got, ref)
+
+
+def test_ws64_rule_copy_limits():
+    """hip_checks.ws64_tile, the copy of the engine's akgm_ws64 rule the val-shape tests assert the dispatch with: the halo of
+    a 128-position tile fits up to width 69, that of a 64-position tile up to 101, wider planes fall back; small grids take
+    64-position tiles or the fallback.  Values for 256 CUs (MI355X)."""
+    for w, t in ((68, 128), (69, 128), (70, 64), (72, 64), (100, 64), (101, 64), (102, 0), (104, 0), (208, 0)):
+        assert C.ws64_tile(64, 36, w, 256) == t, (w, t)
+    assert C.ws64_tile(1, 52, 52, 256) == 0                   # B = 1 at 52^2, the DDPM.test geometry: one-shot kernel
+    assert C.ws64_tile(16, 52, 52, 256) == 128 and C.ws64_tile(5, 26, 26, 256) == 64
+    assert C.ws64_tile(1, 104, 26, 256) == 0 and C.ws64_tile(2, 104, 26, 256) == 64    # 5820 vs 5856 positions: just short
+    assert C.ws64_tile(1, 208, 52, 256) == 128                # a tall plane: 88 tiles per sample
+    assert C.ws64_tile(64, 180, 180, 256) == 0                # (H + 2)(W + 2) >= 32768
+    from ucdir_amd.spec import UNetConfig
+    sid = UNetConfig(inner_channel=64, channel_mults=(1, 2, 4, 8, 8), res_blocks=2, attn_res=(16,), image_size=128)
+    assert C.ws64_prediction(sid, 2, 416, 544, 256) == {3: (52, 68, 64, 5), 4: (26, 34, 0, 7)}
+
+
+def test_shifted_strip_control_fails_the_tile_bound():
+    """The negative control of the val-shape tests (hip_checks.shift_last_strip) on a level-3 plane of a 416 x 544 forward:
+    a correct layer (a 3x3 conv output plus the worst measured layer-vs-emulation noise) passes both bounds, the copy with
+    its last 32 columns one row down fails the tile bound, and only those columns change."""
+    _, _, got, _, emu = _conv_pair(1, 64, 64, 52, 68, seed=6)
+    ref = C.bfr(emu.float())
+    ok = C.metrics(ref + 6.7e-4 * ref.pow(2).mean().sqrt() * torch.randn(ref.shape, generator=C.rng(7)), ref)
+    assert ok["rel_rms"] < C.EMU_LAYER_TOL and ok["tile_max"] < C.EMU_TILE_TOL, ok
+    bad = C.shift_last_strip(got)
+    assert torch.equal(bad[..., :36], got[..., :36]) and torch.equal(bad[..., 0, :], got[..., 0, :])
+    assert torch.equal(bad[..., 1:, 36:], got[..., :-1, 36:])
+    m = C.metrics(bad, ref)
+    print("shifted strip:", m)
+    assert m["tile_max"] > 100 * C.EMU_TILE_TOL, m
