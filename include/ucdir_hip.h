@@ -116,6 +116,10 @@ int32_t ucdir_sampler_step(float* x_t, const float* eps, const float* noise, int
 /* The same update with its noise generated in registers (ABI 3): element i at step `step` gets the standard normal
  * Philox4x32-10(key = seed, counter = (i / 4, step)) -> Box-Muller value number i % 4 - a function of (seed, step, i) only, so
  * every rank of a sharded restoration draws the same noise without a generator or a broadcast, and no noise tensor exists.
+ * In words: group g = i / 4 draws r0..r3 = Philox4x32-10 with counter (g low 32 bits, g high 32 bits, step, 0x55434449) and key
+ * (seed low 32 bits, seed high 32 bits); u_j = ((r_j >> 9) + 0.5) * 2^-23 lies in (0, 1); elements 4g, 4g + 1 are
+ * sqrt(-2 ln u0) * (cos 2 pi u1, sin 2 pi u1) and 4g + 2, 4g + 3 the same of (u2, u3).  The device evaluates ln, sin and cos with
+ * fast approximations: a few fp32 ulps of |z| from the exact values (oracle/ucdir_oracle.py philox_normal is the float64 statement).
  * ucdir_fill_normal writes the same stream into a buffer (x_T = step 0).  Pointers 16-byte aligned. */
 int32_t ucdir_sampler_step_rng(float* x_t, const float* eps, int64_t n,
                                float c_recip, float c_recipm1, float coef1, float coef2, float sigma,

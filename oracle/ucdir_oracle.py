@@ -642,6 +642,62 @@ def ddpm_test(sd: SD, tab: dict, sr: torch.Tensor, noises, continous: bool = Fal
     return out[..., pd:-pd, pd:-pd]
 
 
+# ----------------------------------------------------------------------------------------------
+# the sampler's counter-based noise (the stream include/ucdir_hip.h states for ucdir_fill_normal,
+# ucdir_sampler_step_rng, ucdir_fewstep_update and their _batched forms)
+# ----------------------------------------------------------------------------------------------
+_M32 = np.uint64(0xFFFFFFFF)
+PHILOX_TAG = 0x55434449          # the fourth counter word
+
+
+def philox4x32_10(ctr, key) -> np.ndarray:
+    """Philox4x32-10 (Salmon, Moraes, Dror, Shaw, SC'11 "Parallel random numbers: as easy as 1, 2, 3"; Random123's
+    philox4x32): ``ctr`` (..., 4) and ``key`` (..., 2) of 32-bit words -> (..., 4) uint64 holding 32-bit words.
+    Round: (c0, c1, c2, c3) -> (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)); the key is bumped by the
+    Weyl constants before every round but the first."""
+    ctr = np.asarray(ctr, dtype=np.uint64) & _M32
+    key = np.asarray(key, dtype=np.uint64) & _M32
+    c0, c1, c2, c3 = (ctr[..., i] for i in range(4))
+    k0, k1 = key[..., 0], key[..., 1]
+    M0, M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
+    W0, W1 = np.uint64(0x9E3779B9), np.uint64(0xBB67AE85)
+    for r in range(10):
+        if r:
+            k0, k1 = (k0 + W0) & _M32, (k1 + W1) & _M32
+        p0, p1 = M0 * c0, M1 * c2                    # 32 x 32 -> 64 bits: exact in uint64
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & _M32, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & _M32
+    return np.stack(np.broadcast_arrays(c0, c1, c2, c3), axis=-1)
+
+
+def philox_u23(words) -> np.ndarray:
+    """32-bit word -> uniform in (0, 1): its top 23 bits plus one half, times 2^-23 (exact in fp32 and float64)."""
+    return ((np.asarray(words, dtype=np.uint64) >> np.uint64(9)).astype(np.float64) + 0.5) * 2.0 ** -23
+
+
+def philox_normal(n: int, seed: int, step: int, per: Optional[int] = None, seeds: Optional[Sequence[int]] = None,
+                  first: int = 0) -> np.ndarray:
+    """Float64 standard normals of the sampler's stream, elements ``first`` ... ``first + n - 1`` (``first`` a multiple of 4).
+    Group g = element // 4 draws Philox4x32-10 with counter (g mod 2^32, g div 2^32, step, 0x55434449) and key (seed mod 2^32,
+    seed div 2^32), the seed taken as its uint64 bit pattern; the words r0..r3 become u_i = philox_u23(r_i) and
+    z = sqrt(-2 ln u1) (cos 2 pi u2, sin 2 pi u2) for the pairs (r0, r1) -> elements 4g, 4g + 1 and (r2, r3) -> 4g + 2, 4g + 3.
+    ``seeds``: n = per * len(seeds), sample b draws the stream of seeds[b] with elements counted from its own start."""
+    if seeds is not None:
+        if per is None or per % 4 or n != per * len(seeds):
+            raise ValueError("per-sample streams need n = per * len(seeds), per a multiple of 4")
+        return np.concatenate([philox_normal(per, s, step) for s in seeds]) if len(seeds) else np.zeros(0)
+    if first % 4:
+        raise ValueError("first must be a multiple of 4")
+    seed = int(seed) & (2 ** 64 - 1)
+    g = np.arange(first // 4, (first + n + 3) // 4, dtype=np.uint64)
+    ctr = np.stack([g & _M32, g >> np.uint64(32), np.full_like(g, int(step) & 0xFFFFFFFF), np.full_like(g, PHILOX_TAG)], axis=-1)
+    u = philox_u23(philox4x32_10(ctr, [seed & 0xFFFFFFFF, seed >> 32]))
+    z = np.empty(u.shape, dtype=np.float64)
+    for h in (0, 2):
+        rad = np.sqrt(-2.0 * np.log(u[:, h]))
+        z[:, h], z[:, h + 1] = rad * np.cos(2 * np.pi * u[:, h + 1]), rad * np.sin(2 * np.pi * u[:, h + 1])
+    return z.reshape(-1)[:n]
+
+
 def tensor2img(t: torch.Tensor) -> np.ndarray:
     """core/metrics.py:14-34 for a single (3,H,W) / (1,3,H,W) image: clamp, [-1,1] -> uint8 HWC RGB."""
     t = t.squeeze().float().clamp(-1, 1)

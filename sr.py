@@ -44,6 +44,22 @@ def apply_sampler_flags(opt, args):
     return opt
 
 
+def image_seed_base(seed):
+    """Base of the per-image noise seeds: ``seed`` when given, else a draw from torch's CPU generator.  With an initialised process
+    group of more than one rank the draw is rank 0's, broadcast to all: every rank must derive the same streams (a sharded image's
+    x_T and step noise), and a rank whose CPU generator was consumed earlier would otherwise draw another base."""
+    if seed is not None:
+        return seed
+    base = int(torch.randint(0, 2 ** 31, (1,)).item())
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        dev = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend() == "nccl" else torch.device("cpu")
+        t = torch.tensor([base], dtype=torch.int64, device=dev)
+        dist.broadcast(t, src=0)
+        base = int(t.item())
+    return base
+
+
 def make_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument("-c", "--config", type=str, default="config/sid.yaml")
@@ -61,7 +77,7 @@ def make_parser():
     parser.add_argument("--max-images", type=int, default=-1)
     parser.add_argument("--batch", type=int, default=16,
                         help="restore up to this many same-sized val images per DDPM.test call (1: the reference's one-by-one loop)")
-    parser.add_argument("--seed", type=int, default=None, help="base of the per-image noise seeds (default: one random draw per run)")
+    parser.add_argument("--seed", type=int, default=None, help="base of the per-image noise seeds (default: drawn from torch's CPU generator on rank 0)")
     parser.add_argument("--sampler", choices=["ddpm", "ddim", "dpm_solver++"], default=None,
                         help="restore with this sampler (overrides model.sampler of the YAML; ddpm: the T-step ancestral sampler)")
     parser.add_argument("--sampler-steps", type=int, default=None, help="network calls of a ddim / dpm_solver++ restoration")
@@ -115,8 +131,9 @@ def main(argv=None):
     dn = diffusion.netG.denoise_fn
     thr = dn.patch_threshold
     # Per-image noise streams: image i draws Philox(seed_base + 1000003 i) with counters local to the image, whatever batch or rank it is
-    # restored in.  --seed fixes the base; without it one draw from torch's CPU generator per run (torch.manual_seed makes it reproducible).
-    diffusion.image_seed_base = args.seed if args.seed is not None else int(torch.randint(0, 2 ** 31, (1,)).item())
+    # restored in.  --seed fixes the base; without it rank 0 draws it from torch's CPU generator and broadcasts it (the generator's
+    # default seed is fixed, so runs get the same base unless torch.manual_seed or an earlier draw moves it).
+    diffusion.image_seed_base = image_seed_base(args.seed)
     t_restore, n_restored = 0.0, 0
     group_times = []                                              # (images, seconds) of every DDPM.test call (the first one packs the weights)
 

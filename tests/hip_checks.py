@@ -47,6 +47,15 @@ PRED_ELEM_TOL = 6e-2   # ... worst 3.93e-2 (1 x 256^2)
 ATT_EMU_TOL = 2.5e-3   # attention vs self_attention_emu, rel-RMS of the branch: worst 1.62e-3 (C = 384, N = 4096, flash)
 ATT_EMU_TILE_TOL = 3e-3  # ... worst 1.98e-3 (C = 512, N = 1296, B = 2, flash)
 ATT_EMU_ELEM_TOL = 6e-2  # ... worst 3.90e-2 (C = 512, N = 16384, flash)
+# the in-kernel Philox noise against oracle.philox_normal in float64 (tests/test_noise_stream_gpu.py); the kernel's __logf, v_sin_f32 and
+# v_cos_f32 are approximations, so z agrees to a few fp32 ulps of |z| <= 5.77.  tests/test_noise_stream_cpu.py shows every modelled
+# fault of the stream's statement exceeds NOISE_Z_TOL by orders of magnitude
+NOISE_Z_TOL = 1.2e-6   # max |dz| over every element drawn: worst 7.91e-7 (fill_normal_, seed 1234; at |z| ~ 4.4); per-sample streams
+                       # 4.57e-7; the elements with |z| < 1 are within 7.7e-7 relative
+NOISE_LOOP_TOL = 4e-2  # a T = 8 / DDIM / DPM-Solver++ restoration (small configuration) on kernel noise against the same restoration fed
+                       # philox_normal: max |dx| of the result, worst 2.67e-2 (p_sample_loop, one stream).  The bf16 forward turns the
+                       # ulp-level difference in x_t into another realisation of its rounding noise; the graph-replayed DDIM run stays at 8.9e-7
+NOISE_LOOP_RMS_TOL = 8e-3  # ... rel-RMS, worst 5.20e-3 (DDIM eta = 1, B = 2).  Noise counters off by one step: max |dx| >= 2.0, rel-RMS >= 0.76
 
 
 def bfr(t):
@@ -656,6 +665,21 @@ def predictor_emu_case(net, sd, B, H, W, seed=3, samples=None):
         res["upper"].update({k: max(v, res["upper"].get(k, 0.0)) for k, v in hl.upper.items()})
         res["finite"].update({k: v and res["finite"].get(k, True) for k, v in hl.finite.items()})
     return res, got, x
+
+
+def fewstep_formula(coef, x, eps, m, z):
+    """ucdir_fewstep_update in float64 on float64 tensors: (x <- ..., m_prev <- x0) for coef = (c_recip, c_recipm1, flags, p, q, r,
+    b1, store_m, sigma), each coefficient rounded to the fp32 the kernel takes."""
+    from ucdir_amd.ucdir import FEWSTEP_CLIP, FEWSTEP_FACTORED
+    c_recip, c_recipm1, flags, p, q, r, b1, store_m, sigma = coef
+    f32 = lambda v: float(np.float32(v))
+    if flags & FEWSTEP_FACTORED:
+        x0 = f32(c_recip) * (x - f32(c_recipm1) * eps)
+    else:
+        x0 = f32(c_recip) * x - f32(c_recipm1) * eps
+    if flags & FEWSTEP_CLIP:
+        x0 = x0.clamp(-1.0, 1.0)
+    return f32(p) * x0 + f32(q) * x + f32(r) * eps + f32(b1) * m + f32(sigma) * z, x0
 
 
 def sampler_step_case(seed=0):

@@ -62,15 +62,7 @@ def test_update_kernel_matches_float64_formula(case, shape):
     fewstep_update_(xd, ed, md if need_m else None, c_recip, c_recipm1, flags, p, q, r, b1, store_m, sigma,
                     seed=5, step=3, noise=nd if sigma else None)
     torch.cuda.synchronize()
-    f32 = lambda v: float(np.float32(v))                       # the kernel takes fp32 coefficients
-    x64, e64, m64, n64 = (t.double() for t in (x, eps, m, nz))
-    if flags & FEWSTEP_FACTORED:
-        x0 = f32(c_recip) * (x64 - f32(c_recipm1) * e64)
-    else:
-        x0 = f32(c_recip) * x64 - f32(c_recipm1) * e64
-    if flags & FEWSTEP_CLIP:
-        x0 = x0.clamp(-1.0, 1.0)
-    ref = f32(p) * x0 + f32(q) * x64 + f32(r) * e64 + f32(b1) * m64 + f32(sigma) * n64
+    ref, x0 = C.fewstep_formula(CASES[case], *(t.double() for t in (x, eps, m, nz)))
     scale = max(ref.abs().max().item(), 1.0)
     assert (xd.cpu().double() - ref).abs().max().item() <= 1e-6 * scale
     if store_m:

@@ -243,13 +243,14 @@ class GaussianDiffusion(nn.Module):
         return ret
 
     def _seeds_tensor(self, x):
-        """The per-sample Philox keys of ``sample_seeds`` on the device (None: one stream of ``_kseed``, or injected noise)."""
+        """The per-sample Philox keys of ``sample_seeds`` on the device (None: one stream of ``_kseed``, or injected noise): each
+        seed's uint64 bit pattern (``int(v) & (2**64 - 1)``, the key the single-stream wrappers pass) stored as an int64."""
         if self.sample_seeds is None or self.noise_source is not None:
             return None
         B = x.shape[0]
         if len(self.sample_seeds) != B:
             raise ValueError("sample_seeds holds %d seeds for a batch of %d" % (len(self.sample_seeds), B))
-        return torch.tensor([int(v) % (2 ** 63) for v in self.sample_seeds], dtype=torch.int64, device=x.device)
+        return torch.tensor([(int(v) + 2 ** 63) % 2 ** 64 - 2 ** 63 for v in self.sample_seeds], dtype=torch.int64, device=x.device)
 
     def _loop_buffers(self, x, seeds):
         """(cond, x_t, eps, level) of a sampling loop, x_t holding x_T (step 0 of the noise stream, or the injected noise k = 0)."""
