@@ -170,6 +170,16 @@ int32_t ucdir_image_metrics(const float* a, int64_t a_sn, int64_t a_sc, int64_t 
                             int32_t B, int32_t C, int32_t H, int32_t W,
                             void* workspace, uint64_t* sse, double* ssim_sum, void* stream);
 
+/* JPEG round trip of the JPEG-restoration val task (additive in ABI 5; the reference degrades every HR crop with cv2.imencode('.jpg',
+ * quality) + cv2.imdecode, data/LRHR_dataset.py:446-516): baseline encode at `quality` (1..100) and decode, byte for byte what
+ * libjpeg-turbo's defaults (4:2:0, ISLOW DCT, fancy upsampling; Pillow's Image.save(JPEG, quality) + convert("RGB")) make of the
+ * image.  in, out: (B, H, W, 3) uint8, HWC, contiguous, H and W at least 16 (in == out is allowed).  bgr != 0: channel 0 is B and
+ * channel 2 is R, in and out (what cv2 does to an RGB array).  workspace: device buffer of ucdir_jpeg_roundtrip_workspace_bytes(B,
+ * H, W) bytes (-1 on a bad shape), 8-byte aligned.  No synchronisation and no allocation. */
+int64_t ucdir_jpeg_roundtrip_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int32_t ucdir_jpeg_roundtrip(const uint8_t* in, uint8_t* out, int32_t B, int32_t H, int32_t W,
+                             int32_t quality, int32_t bgr, void* workspace, void* stream);
+
 /* ---- introspection (tests / profiling) ---------------------------------------------------
  * Copy the activation a layer produced in the last forward into dst as (B,C,Hc,Wc) fp32 NCHW
  * (Hc, Wc = compute size).  layer = state_dict prefix ("downs.0", "ups.7", "mid.0", ...),

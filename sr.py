@@ -30,7 +30,17 @@ sys.path.insert(0, ROOT)
 from ucdir_amd import config as Config  # noqa: E402
 from ucdir_amd import metrics as Metrics  # noqa: E402
 from ucdir_amd import model as Model  # noqa: E402
-from ucdir_amd.data import PairDataset  # noqa: E402
+from ucdir_amd.data import ImagenetJPGDataset, PairDataset  # noqa: E402
+
+VAL_DATASETS = {"PairDataset": PairDataset, "ImagenetJPGDataset": ImagenetJPGDataset}
+
+
+def make_val_dataset(val_opt):
+    """The val loader named by ``datasets.val.datasetname`` (reference data/__init__.py:59-61; absent: PairDataset)."""
+    name = val_opt.get("datasetname") or "PairDataset"
+    if name not in VAL_DATASETS:
+        raise ValueError("datasets.val.datasetname %r is not supported by -p val (known: %s)" % (name, ", ".join(VAL_DATASETS)))
+    return VAL_DATASETS[name](val_opt["data_args"], phase="val")
 
 
 def apply_sampler_flags(opt, args):
@@ -110,7 +120,7 @@ def main(argv=None):
     fh = logging.FileHandler(os.path.join(opt["path"]["log"], "val.log"))
     logging.getLogger("val").addHandler(fh)
 
-    val_set = PairDataset(opt["datasets"]["val"]["data_args"], phase="val")
+    val_set = make_val_dataset(opt["datasets"]["val"])
     if args.synthetic_weights:
         opt["path"]["resume_state"] = None
     diffusion = Model.create_model(opt)

@@ -31,6 +31,7 @@
 #include "misc.hip.h"
 #include "fewstep.hip.h"
 #include "image_metrics.hip.h"
+#include "jpeg_roundtrip.hip.h"
 #include "pack.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -1898,6 +1899,58 @@ int32_t ucdir_image_metrics(const float* a, int64_t a_sn, int64_t a_sc, int64_t 
     HIPC(hipGetLastError());
     hipLaunchKernelGGL(image_metrics_finish_kernel, dim3((unsigned)(B * C)), dim3(256), 0, (hipStream_t)stream, part_ssim, part_sse,
                        (int)ntiles, (int)(H > 10 && W > 10), (unsigned long long*)sse, ssim_sum);
+    HIPC(hipGetLastError());
+    API_END
+}
+
+// JPEG round trip of the JPEG-restoration val task (csrc/jpeg_roundtrip.hip.h): the Y plane of the 16-padded image and two half-size
+// chroma planes per image
+int64_t ucdir_jpeg_roundtrip_workspace_bytes(int32_t B, int32_t H, int32_t W) {
+    if (B <= 0 || H < 16 || W < 16) return -1;
+    const int64_t H16 = (H + 15) & ~15, W16 = (W + 15) & ~15;
+    return (int64_t)B * H16 * W16 * 3 / 2;
+}
+
+int32_t ucdir_jpeg_roundtrip(const uint8_t* in, uint8_t* out, int32_t B, int32_t H, int32_t W, int32_t quality, int32_t bgr,
+                             void* workspace, void* stream) {
+    API_BEGIN
+    const std::string w("ucdir_jpeg_roundtrip");
+    require(quality >= 1 && quality <= 100, w + ": quality must lie in 1..100");
+    require(B > 0 && H >= 16 && W >= 16, w + ": bad shape (B > 0, H and W at least 16)");
+    require((int64_t)B * H * W < (1LL << 31), w + ": more than 2^31 - 1 pixels");
+    require(in && out && workspace, w + ": null argument");
+    require(((uintptr_t)workspace & 7) == 0, w + ": workspace must be 8-byte aligned");
+    hipPointerAttribute_t pa;
+    HIPC(hipPointerGetAttributes(&pa, in));
+    require(pa.type == hipMemoryTypeDevice, w + ": in is not a device pointer");
+    const void* others[2] = {out, workspace};
+    const char* names[2] = {"out", "workspace"};
+    for (int i = 0; i < 2; ++i) {
+        hipPointerAttribute_t po;
+        HIPC(hipPointerGetAttributes(&po, others[i]));
+        require(po.type == hipMemoryTypeDevice && po.device == pa.device, w + ": " + names[i] + " must live on the device of in");
+    }
+    // Annex K tables with IJG quality scaling (jcparam.c jpeg_quality_scaling + jpeg_add_quant_table, force_baseline)
+    static const int std_luma[64] = {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56,
+                                     14, 17, 22, 29, 51, 87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92,
+                                     49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
+    static const int std_chroma4[16] = {17, 18, 24, 47, 18, 21, 26, 66, 24, 26, 56, 99, 47, 66, 99, 99};
+    const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+    JpegQuant qt;
+    for (int i = 0; i < 64; ++i) {
+        const int r = i >> 3, c = i & 7;
+        const int sc = (r < 4 && c < 4) ? std_chroma4[r * 4 + c] : 99;
+        qt.q[0][i] = std::min(std::max((std_luma[i] * scale + 50) / 100, 1), 255);
+        qt.q[1][i] = std::min(std::max((sc * scale + 50) / 100, 1), 255);
+    }
+    DevGuard dg(pa.device);
+    const long long nmcu = (long long)B * ((H + 15) / 16) * ((W + 15) / 16);
+    hipLaunchKernelGGL(jpeg_mcu_kernel, dim3((unsigned)((nmcu + JPEG_MCUS_PER_WG - 1) / JPEG_MCUS_PER_WG)), dim3(256), 0,
+                       (hipStream_t)stream, in, (unsigned char*)workspace, B, H, W, bgr ? 1 : 0, qt);
+    HIPC(hipGetLastError());
+    const long long npix = (long long)B * H * W;
+    hipLaunchKernelGGL(jpeg_upsample_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const unsigned char*)workspace, out, B, H, W, bgr ? 1 : 0);
     HIPC(hipGetLastError());
     API_END
 }

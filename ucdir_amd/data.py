@@ -1,6 +1,6 @@
-"""Minimal paired-image loader for ``-p val`` (reference: data/LRHR_dataset.py:230-297 PairDataset,
-val split, datatype img): sorted file lists of dataroot.lq / dataroot.gt, RGB, scaled to [-1, 1]
-(data/util.py:76-83), dict with 'HR', 'SR', 'LR', 'Index'."""
+"""Paired-image loader for ``-p val`` (reference: data/LRHR_dataset.py:230-297 PairDataset, val split, datatype img):
+sorted file lists of dataroot.lq / dataroot.gt, RGB, scaled to [-1, 1] (data/util.py:76-83), dict with 'HR', 'SR', 'LR',
+'Index'; and the JPEG-restoration loader ImagenetJPGDataset (reference: data/LRHR_dataset.py:446-516)."""
 import os
 
 import numpy as np
@@ -37,3 +37,70 @@ class PairDataset:
     def __getitem__(self, i):
         sr, hr = _load(self.sr_path[i]), _load(self.hr_path[i])
         return {"HR": hr, "SR": sr, "LR": sr, "Index": i}
+
+
+# u8 -> [-1, 1] exactly as _load forms it (numpy fp32 u8 / 255, then * 2 - 1 in torch fp32), as a 256-entry table: a division by a
+# scalar on the GPU multiplies by the reciprocal and can land one ulp away
+_U8_TO_UNIT = torch.from_numpy(np.arange(256, dtype=np.float32) / 255.0) * 2.0 - 1.0
+_unit_tables = {}
+
+
+def _u8_to_unit(x):
+    """(H, W, 3) uint8 on a device -> (3, H, W) fp32 in [-1, 1] on that device."""
+    lut = _unit_tables.get(x.device)
+    if lut is None:
+        lut = _unit_tables[x.device] = _U8_TO_UNIT.to(x.device)
+    return lut[x.long()].permute(2, 0, 1).contiguous()
+
+
+class ImagenetJPGDataset:
+    """JPEG-restoration val loader (reference: data/LRHR_dataset.py:446-516, ImagenetJPGDataset): file names from the first field
+    of each line of dataroot.txt under dataroot.root; HR = a centered crop of the RGB image; SR = HR after a JPEG round trip at
+    quality factor ``factor``, computed on the current GPU (csrc/jpeg_roundtrip.hip.h) with the reference's cv2 channel order.
+
+    The quality factor is ``factor[0]`` when both ends agree (the ``jpg-`` val setting, [10, 10]); otherwise it is drawn from a
+    generator seeded by the image index, not from numpy's global RNG as the reference does, so an image's degradation does not
+    depend on rank, batch or order."""
+
+    def __init__(self, data_args, phase="val"):
+        root = data_args["dataroot"]
+        self.root = root["root"]
+        with open(root["txt"]) as f:
+            names = [ln.split()[0] for ln in f if ln.strip()]
+        n = data_args.get("data_len", -1)
+        if n and n > 0:
+            names = names[:n]
+        self.hr_path = [os.path.join(self.root, s) for s in names]
+        self.sr_path = self.hr_path                  # sr.py names its outputs after sr_path
+        self.crop_size = data_args.get("crop_size") or 0
+        self.factor = list(data_args.get("factor") or [5, 5])
+
+    def __len__(self):
+        return len(self.hr_path)
+
+    def load_u8(self, i):
+        """Host half: decode to RGB and crop -> (H, W, 3) uint8, contiguous.  The reference names PIL's (width, height) h, w; the
+        crop below is the one it takes."""
+        from PIL import Image
+        img = Image.open(self.hr_path[i]).convert("RGB")
+        cs = self.crop_size
+        if min(img.size) < cs:
+            img = img.resize((cs, cs))
+        w, h = img.size
+        cw, ch = (cs, cs) if cs > 0 else (w // 16 * 16, h // 16 * 16)
+        left, top = (w - cw) // 2, (h - ch) // 2
+        img = img.crop((left, top, left + cw, top + ch))
+        return np.array(img, dtype=np.uint8)             # a writable copy (torch.from_numpy of PIL's read-only view warns)
+
+    def quality(self, i):
+        lo, hi = int(self.factor[0]), int(self.factor[1])
+        if lo == hi:
+            return lo
+        return int(np.random.RandomState(i).randint(lo, hi + 1))
+
+    def __getitem__(self, i):
+        from .metrics import jpeg_roundtrip_device
+        hr_u8 = torch.from_numpy(self.load_u8(i)).to(torch.device("cuda", torch.cuda.current_device()))
+        sr_u8 = jpeg_roundtrip_device(hr_u8, self.quality(i), bgr=True)
+        sr = _u8_to_unit(sr_u8)
+        return {"HR": _u8_to_unit(hr_u8), "SR": sr, "LR": sr, "Index": i}

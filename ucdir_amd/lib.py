@@ -52,6 +52,8 @@ _SIGS = {
     "ucdir_image_metrics_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "ucdir_image_metrics": (c_int32, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int32, c_int32,
                                       c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ucdir_jpeg_roundtrip_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32]),
+    "ucdir_jpeg_roundtrip": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "ucdir_sampler_step": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float,
                                      c_float, c_void_p]),
     "ucdir_debug_read": (c_int32, [c_void_p, c_char_p, c_char_p, c_void_p, c_int64, c_void_p]),

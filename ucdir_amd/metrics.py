@@ -106,3 +106,33 @@ def psnr_ssim_device(sr, hr):
             ssim.append(float(np.mean([ssim_h[n * C + c] / ((H - 10) * (W - 10)) for c in range(C)])))
     return psnr, ssim
 
+
+
+def jpeg_roundtrip_device(x_u8, quality, bgr=True):
+    """JPEG encode at ``quality`` + decode of uint8 images on the GPU (csrc/jpeg_roundtrip.hip.h): byte for byte what libjpeg-turbo's
+    defaults (4:2:0, ISLOW DCT; Pillow's Image.save(JPEG, quality) + convert("RGB")) make of them.  ``x_u8``: (B, H, W, 3) or
+    (H, W, 3) contiguous uint8 CUDA tensor, H and W at least 16 -> a new tensor of the same shape on the same device, computed on
+    the current stream.  bgr=True (the default) reproduces the reference's cv2.imencode / cv2.imdecode of an RGB array, which
+    libjpeg reads as BGR (data/LRHR_dataset.py:505-506); bgr=False is the plain RGB round trip."""
+    import torch
+    from . import lib
+    from .ucdir import _ptr, _stream_ptr
+    if not torch.is_tensor(x_u8) or not x_u8.is_cuda:
+        raise ValueError("jpeg_roundtrip_device takes a uint8 tensor on the GPU")
+    if x_u8.dtype != torch.uint8:
+        raise ValueError(f"jpeg_roundtrip_device takes uint8 images, got {x_u8.dtype}")
+    if x_u8.dim() not in (3, 4) or x_u8.shape[-1] != 3:
+        raise ValueError(f"jpeg_roundtrip_device takes (B, H, W, 3) or (H, W, 3) images, got {tuple(x_u8.shape)}")
+    if not x_u8.is_contiguous():
+        raise ValueError("jpeg_roundtrip_device takes a contiguous tensor")
+    if isinstance(quality, bool) or int(quality) != quality or not 1 <= quality <= 100:
+        raise ValueError(f"jpeg_roundtrip_device: quality must be an integer in 1..100, got {quality!r}")
+    x = x_u8 if x_u8.dim() == 4 else x_u8.unsqueeze(0)
+    B, H, W, _ = x.shape
+    if H < 16 or W < 16:
+        raise ValueError(f"jpeg_roundtrip_device: H and W must be at least 16, got {H} x {W}")
+    L = lib.load()
+    ws = torch.empty(L.ucdir_jpeg_roundtrip_workspace_bytes(B, H, W), dtype=torch.uint8, device=x.device)
+    out = torch.empty_like(x_u8)
+    lib.check(L.ucdir_jpeg_roundtrip(_ptr(x), _ptr(out), B, H, W, int(quality), 1 if bgr else 0, _ptr(ws), _stream_ptr(x.device)))
+    return out
