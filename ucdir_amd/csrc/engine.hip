@@ -174,7 +174,7 @@ static AkgmW upload_akgm(DevPool& pool, const float* wsp, const float* bsp, cons
 // launch helpers
 // ------------------------------------------------------------------------------------------------
 // ---- optional per-launch HIP-event timing (bench.py roofline) -------------------------------------
-struct ProfEntry { int key; double flops; double bytes; hipEvent_t e0, e1; int dH = 0, dW = 0, dCin = 0, dCout = 0; };
+struct ProfEntry { int key; double flops, bytes; int dH, dW, dCin, dCout; hipEvent_t e0 = nullptr, e1 = nullptr; };
 struct Profiler {
     bool on = false;
     std::vector<ProfEntry> entries;
@@ -186,6 +186,98 @@ struct Profiler {
     ~Profiler() { for (auto e : pool) (void)hipEventDestroy(e); }
 };
 static Profiler g_prof;
+
+// Profiler keys: the numbers by which bench.py (KEY_NAMES), tools/layer_detail.py and the GPU tests know which kernel ran.
+enum ProfKey {
+    KEY_CGEMM64 = 0, KEY_CGEMM128 = 100,       // cgemm_kernel<TM, EPI_STD, mode>: + the MODE_* of its column mapping (0 .. 4)
+    KEY_CGEMM_AKGM = 10,                       // cgemm_kernel<TM, EPI_AKGM, MODE_S1>: added to KEY_CGEMM64 | KEY_CGEMM128
+    KEY_HALO64 = 20, KEY_HALO128 = 120,        // conv3x3_halo_kernel<TM>: + KEY_HALO_UP (Upsample parity classes) + KEY_HALO_DUAL (<64, true>)
+    KEY_HALO_UP = 1, KEY_HALO_DUAL = 2,
+    KEY_CONV_WS = 23, KEY_CONV_WS128 = 24, KEY_QKV_WS = 105,
+    KEY_AKGM_HALO = 111, KEY_AKGM_PRE = 112, KEY_AKGM_WS = 113, KEY_AKGM_WS16 = 114, KEY_AKGM_WS32 = 115, KEY_AKGM_WS64 = 116,
+    KEY_CONV_SK8 = 125, KEY_CONV_SK4 = 127,    // conv_sk_kernel<., 8 | 4, 9>: + KEY_SK_UP for the Upsample parity classes (<., ., 4>)
+    KEY_SK_UP = 1, KEY_CONV_SK_MIX = 129,      // conv_sk_kernel<1, 4, 9> with wide + short units
+    KEY_FLASH = 130, KEY_FLASH_F16 = 131,
+};
+
+// The launch bracket of every profiled operator: `launch` issues its kernel(s); with the profiler on, HIP events around them and a
+// row for ucdir_profile_read.
+template <typename F> static void bracket(ProfEntry e, hipStream_t st, F launch) {
+    if (g_prof.on) {
+        e.e0 = g_prof.get(); e.e1 = g_prof.get();
+        HIPC(hipEventRecord(e.e0, st));
+        launch();
+        HIPC(hipEventRecord(e.e1, st));
+        g_prof.entries.push_back(e);
+    } else launch();
+    HIPC(hipGetLastError());
+}
+
+// ---- UCDIR_TIMING build (ucdir_amd/build.py --timing): the s_memtime stamps one workgroup leaves behind its `dbg` pointer ---------
+// nwin windows of wlen entries, at most nmax deltas printed per window; a window keeps its stamp count in its last entry (sk, conv_sk_kernel:
+// in the buffer's last entries, counted from the end, and every window prints its start relative to the earlier of the two).
+struct StampLayout { int nwin, wlen, nmax; bool sk; };
+static constexpr StampLayout STAMPS_256{1, 256, 255, false}, STAMPS_CGEMM{1, 64, 60, false}, STAMPS_CONV_WS{2, 256, 255, false}, STAMPS_CONV_SK{2, 128, 120, true};
+// Around one launch: dbg() goes into the kernel's parameters, print() synchronises, copies the stamps back and writes one stderr line per
+// window: header(window, stamps) its prefix, then the deltas of consecutive stamps.  The default build compiles to nothing: dbg stays null.
+struct StampDump {
+#ifdef UCDIR_TIMING
+    static constexpr int CAP = 512;
+    hipStream_t st; StampLayout lay; unsigned long long* buf;
+    StampDump(hipStream_t s, StampLayout l) : st(s), lay(l) {
+        static unsigned long long* dev = nullptr;        // every dump ends with a synchronisation: one buffer serves all launchers
+        if (!dev) HIPC(hipMalloc((void**)&dev, CAP * 8));
+        buf = dev;
+        HIPC(hipMemsetAsync(buf, 0, CAP * 8, st));
+    }
+    unsigned long long* dbg() const { return buf; }
+    template <typename H> void print(H header) const {
+        unsigned long long h[CAP];
+        HIPC(hipStreamSynchronize(st));
+        HIPC(hipMemcpy(h, buf, sizeof(h), hipMemcpyDeviceToHost));
+        for (int w = 0; w < lay.nwin; ++w) {
+            const unsigned long long* s = h + w * lay.wlen;
+            const int n = (int)(lay.sk ? h[lay.nwin * lay.wlen - 1 - w] : s[lay.wlen - 1]);
+            header(w, n);
+            if (lay.sk) fprintf(stderr, " start %llu |", s[0] - (h[0] < h[lay.wlen] ? h[0] : h[lay.wlen]));
+            for (int i = 1; i < n && i < lay.nmax; ++i) fprintf(stderr, " %llu", s[i] - s[i - 1]);
+            fprintf(stderr, "\n");
+        }
+    }
+#else
+    StampDump(hipStream_t, StampLayout) {}
+    unsigned long long* dbg() const { return nullptr; }
+    template <typename H> void print(H) const {}
+#endif
+};
+
+// ---- environment switches: read once per process, when the first of them is asked for -------------------------------------------------
+struct Env {
+    static bool has(const char* n) { return getenv(n) != nullptr; }                                   // set at all
+    static bool is0(const char* n) { const char* v = getenv(n); return v && atoi(v) == 0; }           // set to 0
+    const bool no_pre = has("UCDIR_NO_PRE");                   // AKGM, 8 channels per group: the ring kernel instead of akgm_pre / akgm_ws<8>
+    const bool no_attlds = has("UCDIR_NO_ATTLDS");             // AKGM, 16 / 32 per group: akgm_halo_stage instead of akgm_halo<att-lds>
+    const bool no_ws = has("UCDIR_NO_WS");                     // AKGM: no persistent kernel at all (akgm_ws / ws32 / ws64)
+    const bool no_ws16 = has("UCDIR_NO_WS16");                 // AKGM, C = 128: no akgm_ws<16>
+    const bool no_ws32 = has("UCDIR_NO_WS32");                 // AKGM, C = 256: no akgm_ws32
+    const bool no_ws64 = has("UCDIR_NO_WS64");                 // AKGM, C = 512: akgm_halo_stage instead of akgm_ws64
+    const bool no_owntc = has("UCDIR_NO_OWNTC");               // AKGM: akgm_tc_kernel forms the fold constants for every kernel
+    const bool no_conv_sk = has("UCDIR_NO_CONV_SK");           // conv: no stream-K kernel (ucdir_debug_flag("convsk") overrides)
+    const bool sk_mix = !is0("UCDIR_SK_MIX");                  // conv_sk<1, 4, 9>: wide + short units (=0 off; ucdir_debug_flag("skmix") overrides)
+    const bool no_tail_res = has("UCDIR_NO_TAIL_RES");         // a block's res_conv never rides as the tail workgroups of conv1's launch
+    const bool no_fused_res = has("UCDIR_NO_FUSED_RES");       // ... nor as a 10th tap of conv3x3_halo<64, dual> / conv_ws128
+    const bool no_atile = has("UCDIR_NO_ATILE");               // conv3x3_halo: weights from the [rows][K] matrix, not the tiled stages
+    const bool no_conv_ws = has("UCDIR_NO_CONV_WS");           // 64 -> 64 convs: conv3x3_halo<64> instead of conv_ws
+    const bool no_conv_ws128 = has("UCDIR_NO_CONV_WS128");     // 128 -> 64 + res_conv: conv3x3_halo<64, dual> instead of conv_ws128
+    const bool no_qkv_ws = has("UCDIR_NO_QKV_WS");             // attention: cgemm + transpose instead of qkv_ws
+    const bool no_flash = has("UCDIR_NO_FLASH");               // attention: materialised scores (ucdir_debug_flag("flash") overrides)
+    const bool no_fused_final = has("UCDIR_NO_FUSED_FINAL");   // final_conv: activation pass + MFMA conv instead of final_conv_kernel
+    const bool splitk = !is0("UCDIR_SPLITK");                  // split-K / unit split of under-filled grids (=0 off; ucdir_debug_flag("splitk") overrides)
+    const int splitk_wgs = has("UCDIR_SPLITK_WGS") ? atoi(getenv("UCDIR_SPLITK_WGS")) : 256;   // ... for grids of at most this many workgroups
+    const bool keep_acts = has("UCDIR_KEEP_ACTS");             // large shapes: every activation keeps its own buffer (ucdir_debug_read)
+    const bool prof_detail = has("UCDIR_PROF_DETAIL");         // ucdir_profile_read prints one PROF line per (key, shape)
+};
+static const Env& env() { static const Env e; return e; }
 
 template <int TM, int EPI, int MODE>
 static void launch_one(const GemmP& p, dim3 grid, size_t lds, hipStream_t st) {
@@ -263,60 +355,40 @@ static void gemm_work(const GemmP& p, int epi, double& flops, double& bytes) {
     }
 }
 
-static void launch_cgemm_impl(const GemmP& p, int TM, int epi, hipStream_t st);
-static void launch_cgemm(const GemmP& p, int TM, int epi, hipStream_t st) {
-    if (!g_prof.on) { launch_cgemm_impl(p, TM, epi, st); return; }
-    ProfEntry e;
-    int mode = p.cols_mode; if (mode == COLS_S1 && p.in_compact) mode = MODE_S1C;
-    e.key = (TM == 128 ? 100 : 0) + (epi == EPI_AKGM ? 10 : 0) + (epi == EPI_AKGM ? 0 : mode);
+static ProfEntry gemm_entry(int key, const GemmP& p, int epi, int cin) {
+    ProfEntry e{key, 0, 0, p.H, p.W, cin, p.nfeat};
     gemm_work(p, epi, e.flops, e.bytes);
-    e.dH = p.H; e.dW = p.W; e.dCin = p.cg * p.ntaps; e.dCout = p.nfeat;
-    e.e0 = g_prof.get(); e.e1 = g_prof.get();
-    HIPC(hipEventRecord(e.e0, st));
-    launch_cgemm_impl(p, TM, epi, st);
-    HIPC(hipEventRecord(e.e1, st));
-    g_prof.entries.push_back(e);
+    return e;
+}
+// a block's 1x1 res_conv riding in a 3x3 conv's launch: same input (counted once), its own weights and output
+static void add_res_rider(ProfEntry& e, const GemmP& p) {
+    const double cols = (double)p.H * p.W * p.nbatch;
+    e.flops += 2.0 * p.cg * p.nfeat * cols;
+    e.bytes += 2.0 * p.cg * p.nfeat + 2.0 * p.nfeat * cols;
 }
 
-static void launch_cgemm_impl(const GemmP& p0, int TM, int epi, hipStream_t st) {
-    GemmP p = p0;
-#ifdef UCDIR_TIMING
-    static unsigned long long* cgdbg = nullptr;
-    if (!cgdbg) HIPC(hipMalloc((void**)&cgdbg, 64 * 8));
-    HIPC(hipMemsetAsync(cgdbg, 0, 64 * 8, st));
-    p.dbg = cgdbg;
-    struct Pr { unsigned long long* d; hipStream_t s; int mode, TM, nk; ~Pr() {
-        unsigned long long h[64]; (void)hipStreamSynchronize(s); (void)hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost);
-        const int n = (int)h[63]; fprintf(stderr, "CGEMM TIMING mode=%d TM=%d nk=%d n=%d:", mode, TM, nk, n);
-        for (int i = 1; i < n && i < 60; ++i) fprintf(stderr, " %llu", h[i] - h[i - 1]); fprintf(stderr, "\n"); } } pr{cgdbg, st, p.cols_mode, TM, p.nk};
-#endif
-    const int nblk = p.nbatch * p.tiles * p.rowtiles;
-    const size_t lds = cgemm_lds_bytes(TM, epi, p.groups_per_wg);
-    dim3 grid(nblk);
+template <int TM>
+static void launch_mode(const GemmP& p, int epi, int mode, dim3 grid, size_t lds, hipStream_t st) {
+    if (epi == EPI_AKGM) { launch_one<TM, EPI_AKGM, MODE_S1>(p, grid, lds, st); return; }
+    switch (mode) {
+        case MODE_S1: launch_one<TM, EPI_STD, MODE_S1>(p, grid, lds, st); break;
+        case MODE_DOWN: launch_one<TM, EPI_STD, MODE_DOWN>(p, grid, lds, st); break;
+        case MODE_UP: launch_one<TM, EPI_STD, MODE_UP>(p, grid, lds, st); break;
+        case MODE_PLAIN: launch_one<TM, EPI_STD, MODE_PLAIN>(p, grid, lds, st); break;
+        default: launch_one<TM, EPI_STD, MODE_S1C>(p, grid, lds, st); break;
+    }
+}
+static void launch_cgemm(GemmP p, int TM, int epi, hipStream_t st) {
     int mode = p.cols_mode;
     if (mode == COLS_S1 && p.in_compact) mode = MODE_S1C;
-    if (epi == EPI_AKGM) {
-        if (TM == 128) launch_one<128, EPI_AKGM, MODE_S1>(p, grid, lds, st); else launch_one<64, EPI_AKGM, MODE_S1>(p, grid, lds, st);
-    } else if (TM == 128) {
-        switch (mode) {
-            case MODE_S1: launch_one<128, EPI_STD, MODE_S1>(p, grid, lds, st); break;
-            case MODE_DOWN: launch_one<128, EPI_STD, MODE_DOWN>(p, grid, lds, st); break;
-            case MODE_UP: launch_one<128, EPI_STD, MODE_UP>(p, grid, lds, st); break;
-            case MODE_PLAIN: launch_one<128, EPI_STD, MODE_PLAIN>(p, grid, lds, st); break;
-            default: launch_one<128, EPI_STD, MODE_S1C>(p, grid, lds, st); break;
-        }
-    } else {
-        switch (mode) {
-            case MODE_S1: launch_one<64, EPI_STD, MODE_S1>(p, grid, lds, st); break;
-            case MODE_DOWN: launch_one<64, EPI_STD, MODE_DOWN>(p, grid, lds, st); break;
-            case MODE_UP: launch_one<64, EPI_STD, MODE_UP>(p, grid, lds, st); break;
-            case MODE_PLAIN: launch_one<64, EPI_STD, MODE_PLAIN>(p, grid, lds, st); break;
-            default: launch_one<64, EPI_STD, MODE_S1C>(p, grid, lds, st); break;
-        }
-    }
-    HIPC(hipGetLastError());
+    const dim3 grid(p.nbatch * p.tiles * p.rowtiles);
+    const size_t lds = cgemm_lds_bytes(TM, epi, p.groups_per_wg);
+    StampDump sd(st, STAMPS_CGEMM); p.dbg = sd.dbg();
+    bracket(gemm_entry((TM == 128 ? KEY_CGEMM128 : KEY_CGEMM64) + (epi == EPI_AKGM ? KEY_CGEMM_AKGM : mode), p, epi, p.cg * p.ntaps), st, [&] {
+        if (TM == 128) launch_mode<128>(p, epi, mode, grid, lds, st); else launch_mode<64>(p, epi, mode, grid, lds, st);
+    });
+    sd.print([&](int, int n) { fprintf(stderr, "CGEMM TIMING mode=%d TM=%d nk=%d n=%d:", p.cols_mode, TM, p.nk, n); });
 }
-
 
 static int ilog2(int v) { int s = 0; while ((1 << s) < v) ++s; return s; }
 
@@ -350,35 +422,20 @@ static void choose_tile(int H, int W, int& th, int& tw) {
 }
 
 template <int TM, bool DUAL = false>
-static void launch_halo(const GemmP& p, hipStream_t st) {
+static void launch_halo(GemmP p, hipStream_t st) {
     const int ks = p.ksplit > 1 ? p.ksplit : 1;
     const int nblk = p.nbatch * p.tiles_x * p.tiles_y * p.rowtiles * (p.up_phase ? 4 : 1) * ks + p.alt_blocks;
-    auto finish = [&]() {
+    ProfEntry e = gemm_entry((TM == 128 ? KEY_HALO128 : KEY_HALO64) + (p.up_phase ? KEY_HALO_UP : 0) + (DUAL ? KEY_HALO_DUAL : 0), p, EPI_STD, p.cg);
+    if (p.alt_blocks) add_res_rider(e, p);
+    StampDump sd(st, STAMPS_256); p.dbg = sd.dbg();
+    bracket(e, st, [&] {
+        hipLaunchKernelGGL((conv3x3_halo_kernel<TM, DUAL>), dim3(nblk), dim3(HC_THREADS), hc_lds_bytes<TM>(), st, p);
         if (ks == 1) return;
         const long long items = (long long)p.H * p.W * (p.up_phase ? 4 : 1) * (p.nfeat / 8);
         int gx = (int)((items + 255) / 256); if (gx > 1024) gx = 1024;
         hipLaunchKernelGGL(conv_splitk_finish_kernel, dim3(gx, p.nbatch), dim3(256), 0, st, p, TM);
-    };
-
-    if (g_prof.on) {
-        ProfEntry e; e.key = (TM == 128 ? 120 : 20) + (p.up_phase ? 1 : 0) + (DUAL ? 2 : 0); gemm_work(p, EPI_STD, e.flops, e.bytes);
-        if (p.alt_blocks) {        // the 1x1 res_conv riding in this launch: same input (counted once), its own weights and output
-            const double cols = (double)p.H * p.W * p.nbatch;
-            e.flops += 2.0 * p.cg * p.nfeat * cols;
-            e.bytes += 2.0 * p.cg * p.nfeat + 2.0 * p.nfeat * cols;
-        }
-        e.dH = p.H; e.dW = p.W; e.dCin = p.cg; e.dCout = p.nfeat;
-        e.e0 = g_prof.get(); e.e1 = g_prof.get();
-        HIPC(hipEventRecord(e.e0, st));
-        hipLaunchKernelGGL((conv3x3_halo_kernel<TM, DUAL>), dim3(nblk), dim3(HC_THREADS), hc_lds_bytes<TM>(), st, p);
-        finish();
-        HIPC(hipEventRecord(e.e1, st));
-        g_prof.entries.push_back(e);
-    } else {
-        hipLaunchKernelGGL((conv3x3_halo_kernel<TM, DUAL>), dim3(nblk), dim3(HC_THREADS), hc_lds_bytes<TM>(), st, p);
-        finish();
-    }
-    HIPC(hipGetLastError());
+    });
+    sd.print([](int, int n) { fprintf(stderr, "TIMING n=%d:", n); });
 }
 
 static std::atomic<bool> g_use_halo{true};
@@ -421,15 +478,13 @@ static float* splitk_scratch() {
 // least two chunks per split).  UCDIR_SPLITK=0 disables, UCDIR_SPLITK_WGS sets the grid size below which it applies.
 static std::atomic<int> g_splitk{-1};         // -1: environment (UCDIR_SPLITK=0 disables), 0 / 1: ucdir_debug_flag("splitk", v)
 static bool splitk_on() {
-    static const bool env_on = !(getenv("UCDIR_SPLITK") && atoi(getenv("UCDIR_SPLITK")) == 0);
-    return g_splitk < 0 ? env_on : g_splitk != 0;
+    return g_splitk < 0 ? env().splitk : g_splitk != 0;
 }
 // Cost model in microseconds, fitted to B = 1 kernel traces (profiles/r02_b1_forward_trace.txt): a K step costs ~1.0 us while a
 // CU holds one workgroup (1.3 with two), the finish launch ~5 us + its partial-tile traffic at ~1.5 TB/s.  Deep levels (long
 // K, few outputs) split 8-16 ways; the 144^2 level (10 MB of partial sums per split) never does.
 static int choose_ksplit(int wgs, int nchunks, int steps_per_chunk, double out_elems) {
-    static const int lim = getenv("UCDIR_SPLITK_WGS") ? atoi(getenv("UCDIR_SPLITK_WGS")) : 256;
-    if (!splitk_on() || wgs > lim || wgs <= 0) return 1;
+    if (!splitk_on() || wgs > env().splitk_wgs || wgs <= 0) return 1;
     const double unsplit = (double)nchunks * steps_per_chunk * (wgs > 256 ? 1.3 : 1.0);
     int best = 1;
     double best_cost = 0.85 * unsplit;                  // a split has to be clearly worth its second launch
@@ -458,9 +513,18 @@ static int choose_usplit(int nblk) {
 // ---- conv_sk_kernel (conv_sk.hip.h): persistent stream-K 3x3 conv / Upsample parity classes on 256-row tiles -------------------------
 static std::atomic<int> g_convsk{-1};          // -1: environment (UCDIR_NO_CONV_SK) + work threshold, 0: off, 1: forced (tests: any size)
 static std::atomic<int> g_skmix{-1};           // conv_sk_kernel<1, 4, 9> with wide + short units: -1 environment (UCDIR_SK_MIX=0 off) + its occupancy rule, 0 off, 1 forced at any size (tests)
+// One conv as run_conv takes it and hands it down to the kernel it picks
+struct ConvCall {
+    const Act& x0; const Act* x1; Act& y;      // input (+ the skip tensor concatenated behind it), output
+    int act; const Act* res; bool want_stats;  // epilogue: 0 none | 1 swish | 2 LeakyReLU, residual added, GroupNorm statistics of y
+    Act* res_out = nullptr; const ConvW* wres = nullptr;       // the block's 1x1 res_conv on the same input, asked from the same launch ...
+    float* nchw_out = nullptr; int crop_h = 0, crop_w = 0;     // fp32 (B, cout, crop_h, crop_w) output instead of y
+    bool did_res = false;                                      // ... and whether the launch produced it
+};
 template <int MW, int NW>
-static bool try_conv_sk_mw(const ConvW& w, const Act& x0, const Act* x1, Act& y, bool upph, int act, const Act* res, bool want_stats, hipStream_t st, int mode, bool* did_res, Act* res_out, const ConvW* wres) {
+static bool try_conv_sk_mw(const ConvW& w, ConvCall& c, bool upph, hipStream_t st, int mode) {
     using L = CvSk<MW, NW>;
+    const Act &x0 = c.x0, &y = c.y; const Act* x1 = c.x1;
     const bf16_t* img = upph ? w.Ask_up[MW - 1] : w.Ask[MW - 1];
     if (!img) return false;
     const int cin = x0.C + (x1 ? x1->C : 0);
@@ -491,16 +555,16 @@ static bool try_conv_sk_mw(const ConvW& w, const Act& x0, const Act* x1, Act& y,
     p.inv_per_b = 1.0f / (float)(ns * HpWpe); p.inv_HpWpe = 1.0f / (float)HpWpe; p.inv_Wpe = 1.0f / (float)Wpe;
     p.ntiles = (int)((npos + NPX - 1) / NPX); p.rowtiles = (w.cout + L::ROWS - 1) / L::ROWS; p.npar = upph ? 4 : 1;
     p.nhp = nhp; p.nfeat = w.cout;
-    p.alpha = 1.f; p.fold = (!upph && w.fold) ? 1 : 0; p.act = act;
+    p.alpha = 1.f; p.fold = (!upph && w.fold) ? 1 : 0; p.act = c.act;
     if (p.fold) {
         p.stats0 = x0.stats; p.stats1 = x1 ? x1->stats : nullptr;
         p.inv_count = 1.0 / ((double)cin * H * W);
         p.Tb = w.Tb; p.Tg = w.Tg; p.tab_ld = w.cout;
     }
     p.bias = w.bias;
-    if (res) { p.res = res->p; p.res_ld = res->C; }
+    if (c.res) { p.res = c.res->p; p.res_ld = c.res->C; }
     p.out = y.p; p.out_ld = y.C;
-    if (want_stats) p.stats_out = y.stats;
+    if (c.want_stats) p.stats_out = y.stats;
     p.units = p.npar * p.rowtiles * p.ntiles;
     const long long work = (long long)p.units * p.nchunks;           // chunks of 9 (4) sub-steps
     int G;
@@ -538,7 +602,6 @@ static bool try_conv_sk_mw(const ConvW& w, const Act& x0, const Act* x1, Act& y,
     // and no SIMD more than 1.5 wide wave tiles.  Both unit counts multiples of 8 (an eighth per XCD; wide ones first in every XCD's order).
     bool mix = false;
     if (NW == 4 && MW == 1 && !upph && !ksplit_on && g_persist_grid <= 0 && G == p.units && p.ndp == p.units) {
-        static const bool mix_env = !(getenv("UCDIR_SK_MIX") && atoi(getenv("UCDIR_SK_MIX")) == 0);
         const int force = g_skmix.load();
         const int slots = 2 * num_cus();
         int g8 = 8; while (p.rowtiles % g8) g8 >>= 1;                // gcd(8, rowtiles)
@@ -550,7 +613,7 @@ static bool try_conv_sk_mw(const ConvW& w, const Act& x0, const Act* x1, Act& y,
             wt = step_w;
             nt = p.ntiles - wt; if (nt < 1) nt = 1;
             nt = (nt + step_s - 1) / step_s * step_s;
-        } else if (force < 0 && mix_env && p.units > num_cus() && p.units < slots) {
+        } else if (force < 0 && env().sk_mix && p.units > num_cus() && p.units < slots) {
             nt = slots / p.rowtiles - p.ntiles;                       // rowtiles (wt + 2 nt) <= slots with wt + nt = ntiles
             if (nt > p.ntiles) nt = p.ntiles;
             nt = nt / step_s * step_s;
@@ -567,77 +630,53 @@ static bool try_conv_sk_mw(const ConvW& w, const Act& x0, const Act* x1, Act& y,
             G = p.units + p.mix_nunits;
         }
     }
-    if (did_res) *did_res = false;
-    if (NW == 4 && MW == 1 && !upph && res_out && wres && wres->Ask1x1 && wres->cout == w.cout && ((G == p.units && p.ndp == p.units) || ksplit_on || mix)) {
+    // (8-wave workgroups carry no rider; UCDIR_NO_TAIL_RES keeps it out of this launch as out of conv3x3_halo's)
+    if (NW == 4 && MW == 1 && !upph && !env().no_tail_res && c.res_out && c.wres && c.wres->Ask1x1 && c.wres->cout == w.cout && ((G == p.units && p.ndp == p.units) || ksplit_on || mix)) {
         // the block's 1x1 res_conv as the grid's last workgroups (one per (row tile, pixel tile)): same input, its own weights and output
-        p.alt_units = p.rowtiles * p.ntiles; p.alt_A = wres->Ask1x1; p.alt_bias = wres->bias;
-        p.alt_out = res_out->p; p.alt_out_ld = res_out->C;
+        p.alt_units = p.rowtiles * p.ntiles; p.alt_A = c.wres->Ask1x1; p.alt_bias = c.wres->bias;
+        p.alt_out = c.res_out->p; p.alt_out_ld = c.res_out->C;
         G += p.alt_units;
-        if (did_res) *did_res = true;
+        c.did_res = true;
     }
     const int Gmain = G - p.alt_units;                               // the workgroups of the unit schedule (the finish kernel's view)
     const size_t lds = L::lds_bytes(nhp);
     const int nsk = p.units - p.ndp;
     p.partial = nsk > 0 ? splitk_scratch() : nullptr;                // (no cut unit, no partial tiles: the single-operator entry points do not allocate the scratch for nothing)
-    auto go = [&]() {
+    const double cols = (double)H * W * B * (upph ? 4.0 : 1.0);
+    ProfEntry e{mix ? KEY_CONV_SK_MIX : (NW == 8 ? KEY_CONV_SK8 : KEY_CONV_SK4) + (upph ? KEY_SK_UP : 0),
+                2.0 * 9 * cin * (double)w.cout * cols,               // reference op count (the parity classes execute 4 / 9 of it)
+                ((double)cin * H * W * 2 + (double)w.cout * cols / B * 2) * B + 9.0 * cin * w.cout * 2, H, W, cin, w.cout};
+    if (p.alt_units) { e.flops += 2.0 * cin * (double)w.cout * cols; e.bytes += 2.0 * cin * w.cout + 2.0 * w.cout * cols; }
+    StampDump sd(st, STAMPS_CONV_SK); p.dbg = sd.dbg();
+    bracket(e, st, [&] {
         if (upph) hipLaunchKernelGGL((conv_sk_kernel<MW, NW, 4>), dim3(G), dim3(L::THREADS), lds, st, p);
         else hipLaunchKernelGGL((conv_sk_kernel<MW, NW, 9>), dim3(G), dim3(L::THREADS), lds, st, p);
         if (nsk > 0) hipLaunchKernelGGL((conv_sk_finish_kernel<MW, NW>), dim3(4 * NW, nsk), dim3(64), 0, st, p, Gmain);
-    };
-#ifdef UCDIR_TIMING
-    {
-        static unsigned long long* dbgbuf = nullptr;
-        if (!dbgbuf) HIPC(hipMalloc((void**)&dbgbuf, 256 * 8));
-        HIPC(hipMemset(dbgbuf, 0, 256 * 8));
-        p.dbg = dbgbuf;
-        go();
-        unsigned long long h[256];
-        HIPC(hipStreamSynchronize(st));
-        HIPC(hipMemcpy(h, dbgbuf, sizeof(h), hipMemcpyDeviceToHost));
-        for (int w2 = 0; w2 < 2; ++w2) {
-            const int n = (int)h[255 - w2];
-            fprintf(stderr, "CONV_SK TIMING %s units=%d grid=%d n=%d: start %llu |", w2 ? "last-round" : "first-round", p.units, G, n, h[128 * w2] - (h[0] < h[128] ? h[0] : h[128]));
-            for (int i = 1; i < n && i < 120; ++i) fprintf(stderr, " %llu", h[128 * w2 + i] - h[128 * w2 + i - 1]);
-            fprintf(stderr, "\n");
-        }
-        return true;
-    }
-#endif
-    if (g_prof.on) {
-        ProfEntry e; e.key = mix ? 129 : (NW == 8 ? 125 : 127) + (upph ? 1 : 0);
-        const double cols = (double)H * W * B * (upph ? 4.0 : 1.0);
-        e.flops = 2.0 * 9 * cin * (double)w.cout * cols;             // reference op count (the parity classes execute 4 / 9 of it)
-        e.bytes = ((double)cin * H * W * 2 + (double)w.cout * cols / B * 2) * B + 9.0 * cin * w.cout * 2;
-        if (p.alt_units) { e.flops += 2.0 * cin * (double)w.cout * cols; e.bytes += 2.0 * cin * w.cout + 2.0 * w.cout * cols; }
-        e.dH = H; e.dW = W; e.dCin = cin; e.dCout = w.cout;
-        e.e0 = g_prof.get(); e.e1 = g_prof.get();
-        HIPC(hipEventRecord(e.e0, st));
-        go();
-        HIPC(hipEventRecord(e.e1, st));
-        g_prof.entries.push_back(e);
-    } else go();
-    HIPC(hipGetLastError());
+    });
+    sd.print([&](int win, int n) { fprintf(stderr, "CONV_SK TIMING %s units=%d grid=%d n=%d:", win ? "last-round" : "first-round", p.units, G, n); });
     return true;
 }
 // g_convsk: -1 environment (UCDIR_NO_CONV_SK) + work thresholds, one-shot 4-wave workgroups; 0 off; 1: persistent stream-K workgroups of 8 waves
 // forced; 2: one-shot 4-wave workgroups (two per CU) forced
-static bool try_conv_sk(const ConvW& w, const Act& x0, const Act* x1, Act& y, bool upph, int act, const Act* res, bool want_stats, hipStream_t st, bool* did_res, Act* res_out, const ConvW* wres) {
-    static const bool env_on = !getenv("UCDIR_NO_CONV_SK");
+static bool try_conv_sk(const ConvW& w, ConvCall& c, bool upph, hipStream_t st) {
     const int mode = g_convsk.load();
-    if (mode == 0 || (mode < 0 && !env_on)) return false;
-    if (x0.C % 32 || (x1 && x1->C % 32) || y.C % 8) return false;
+    if (mode == 0 || (mode < 0 && env().no_conv_sk)) return false;
+    if (c.x0.C % 32 || (c.x1 && c.x1->C % 32) || c.y.C % 8) return false;
     const int kind = mode > 0 ? mode : 2;
     const int fm = mode > 0 ? 1 : -1;
-    if (kind == 2) return try_conv_sk_mw<1, 4>(w, x0, x1, y, upph, act, res, want_stats, st, fm, did_res, res_out, wres);
-    if (w.cout % 256 == 0) return try_conv_sk_mw<2, 8>(w, x0, x1, y, upph, act, res, want_stats, st, fm, did_res, nullptr, nullptr);
-    return try_conv_sk_mw<1, 8>(w, x0, x1, y, upph, act, res, want_stats, st, fm, did_res, nullptr, nullptr);
+    if (kind == 2) return try_conv_sk_mw<1, 4>(w, c, upph, st, fm);
+    if (w.cout % 256 == 0) return try_conv_sk_mw<2, 8>(w, c, upph, st, fm);
+    return try_conv_sk_mw<1, 8>(w, c, upph, st, fm);
 }
 
+// The kernels of a conv, in the order they are tried; the stream-K kernel comes before them (try_conv_sk: whether it runs is decided
+// together with its unit schedule)
+enum class ConvKind { WS128, WS, HALO128, HALO64, HALO64_DUAL, CGEMM };
+
 // conv (3x3 stride 1 / down / up, or 1x1) from padded activations to a padded activation
-// res_out != nullptr asks for the block's res_conv output from the same launch; returns true if it was produced
-static bool run_conv(const ConvW& w, const Act& x0, const Act* x1, Act& y, int mode, int act, const Act* res,
-                     bool want_stats, hipStream_t st, float* nchw_out = nullptr, int crop_h = 0, int crop_w = 0,
-                     Act* res_out = nullptr, const ConvW* wres = nullptr) {
+// c.res_out != nullptr asks for the block's res_conv output from the same launch; returns true if it was produced
+static bool run_conv(const ConvW& w, int mode, ConvCall c, hipStream_t st) {
+    const Act &x0 = c.x0, &y = c.y; const Act* x1 = c.x1;
     GemmP p; zero_gemm(p);
     const int cin = x0.C + (x1 ? x1->C : 0);
     require(cin == w.cin, "run_conv: channel mismatch");
@@ -654,16 +693,16 @@ static bool run_conv(const ConvW& w, const Act& x0, const Act* x1, Act& y, int m
     p.tiles = (p.pn + CG_TP - 1) / CG_TP;
     p.rowtiles = w.rows_pad / w.TM;
     p.nbatch = y.B;
-    p.fold = w.fold ? 1 : 0; p.act = act;
+    p.fold = w.fold ? 1 : 0; p.act = c.act;
     if (w.fold) {
         p.stats0 = x0.stats; p.stats1 = x1 ? x1->stats : nullptr;
         p.inv_count = 1.0 / ((double)cin * x0.H * x0.W);
         p.Tb = w.Tb; p.Tg = w.Tg; p.tab_ld = w.cout;
     }
     p.bias = w.bias;
-    if (res) { p.res = res->p; p.res_bstride = res->bstride(); p.res_ld = res->C; p.res_coff = 0; }
+    if (c.res) { p.res = c.res->p; p.res_bstride = c.res->bstride(); p.res_ld = c.res->C; p.res_coff = 0; }
     p.out = y.p; p.out_bstride = y.bstride(); p.out_ld = y.C; p.nfeat = w.cout;
-    if (nchw_out) { p.out = nchw_out; p.out_nchw = 1; p.crop_h = crop_h; p.crop_w = crop_w; }   // fp32 (B, cout, crop_h, crop_w)
+    if (c.nchw_out) { p.out = c.nchw_out; p.out_nchw = 1; p.crop_h = c.crop_h; p.crop_w = c.crop_w; }   // fp32 (B, cout, crop_h, crop_w)
     const bool upph = g_use_halo && mode == COLS_UP && w.Aup && x0.C % 64 == 0 && !x1;
     const bool halo = upph || (g_use_halo && mode == COLS_S1 && w.ntaps == 9 && x0.C % 64 == 0 && (!x1 || x1->C % 64 == 0));
     if (halo) {
@@ -678,75 +717,25 @@ static bool run_conv(const ConvW& w, const Act& x0, const Act* x1, Act& y, int m
             p.tiles *= 4;
         }
     }
-    if (want_stats) {
+    if (c.want_stats) {
         p.stats_out = y.stats;
     }
-    if (halo && !nchw_out) {
-        bool sk_res = false;
-        static const bool sk_tail = !getenv("UCDIR_NO_TAIL_RES");
-        if (try_conv_sk(w, x0, x1, y, upph, act, res, want_stats, st, &sk_res, sk_tail ? res_out : nullptr, wres)) return sk_res;
-    }
-#ifdef UCDIR_TIMING
-    static unsigned long long* dbgbuf = nullptr;
-    if (!dbgbuf) HIPC(hipMalloc((void**)&dbgbuf, 256 * 8));
-    HIPC(hipMemset(dbgbuf, 0, 256 * 8));
-    p.dbg = dbgbuf;
-#endif
+    if (halo && !c.nchw_out && try_conv_sk(w, c, upph, st)) return c.did_res;
+
+    // ---- which kernel: what rides along and how the grid is cut first, then the kernel that fits ------------------------------------
     int tm_run = w.TM;
     if (halo && tm_run == 128 && p.nbatch * p.tiles * p.rowtiles < 256) {
         // too few workgroups for 256 CUs x 2: use 64-row tiles (the packed [rows][K] layout is the same)
         tm_run = 64; p.rowtiles = w.rows_pad / 64;
     }
-    static const bool fuse_res = !getenv("UCDIR_NO_FUSED_RES");
     bool did_res = false;
-    if (halo && !upph && tm_run == 64 && w.TM == 64 && w.A10 && res_out && fuse_res) {
+    if (halo && !upph && tm_run == 64 && w.TM == 64 && w.A10 && c.res_out && !env().no_fused_res) {
         p.A = w.A10; p.a_ld = 10 * cin; p.res_fused = 1; p.bias2 = w.bias_res;
-        p.out2 = res_out->p; p.out2_bstride = res_out->bstride(); p.out2_ld = res_out->C;
+        p.out2 = c.res_out->p; p.out2_bstride = c.res_out->bstride(); p.out2_ld = c.res_out->C;
         did_res = true;
     }
     const bool dual = did_res;                          // conv3x3_halo_kernel<64, true>: second accumulator set
-    static const bool use_atile = !getenv("UCDIR_NO_ATILE");
-    if (use_atile && halo && !upph && !did_res && tm_run == w.TM && w.Atile && w.ntaps == 9) p.A_tiled = w.Atile;
-    // 128 -> 64 with the res_conv fused, on 8 x 16 tiles: persistent kernel with one wave per SIMD (conv_ws128.hip.h)
-    static const bool use_cws128 = !getenv("UCDIR_NO_CONV_WS128");
-    if (use_cws128 && did_res && w.Aws128 && cin == 128 && x0.C == 64 && x1 && x1->C == 64 && !res && !p.out_nchw && y.H % 8 == 0 && y.W % 16 == 0 &&
-        y.C == 64 && (g_persist_grid > 0 || (long long)y.B * (y.H / 8) * (y.W / 16) >= 4LL * num_cus())) {
-        p.A = w.Aws128; p.alt_A = w.Aws128 + (size_t)2 * 72 * 2 * 32 * 8;
-        p.th = 8; p.tw = 16; p.tiles_x = y.W / 16; p.tiles_y = y.H / 8;
-        const int ntiles = y.B * p.tiles_x * p.tiles_y, ncu = num_cus();
-        const int grid = ntiles < ncu ? ntiles : ncu;
-#ifdef UCDIR_TIMING
-        {
-            static unsigned long long* dbgbuf = nullptr;
-            if (!dbgbuf) HIPC(hipMalloc((void**)&dbgbuf, 256 * 8));
-            HIPC(hipMemset(dbgbuf, 0, 256 * 8));
-            p.dbg = dbgbuf;
-            hipLaunchKernelGGL(conv_ws128_kernel, dim3(grid), dim3(CvWs128::THREADS), CvWs128::LDS, st, p);
-            unsigned long long h[256];
-            HIPC(hipStreamSynchronize(st));
-            HIPC(hipMemcpy(h, dbgbuf, sizeof(h), hipMemcpyDeviceToHost));
-            const int n = (int)h[255];
-            fprintf(stderr, "CONV_WS128 TIMING n=%d:", n);
-            for (int i = 1; i < n && i < 255; ++i) fprintf(stderr, " %llu", h[i] - h[i - 1]);
-            fprintf(stderr, "\n");
-            return did_res;
-        }
-#endif
-        if (g_prof.on) {
-            ProfEntry e; e.key = 24; gemm_work(p, EPI_STD, e.flops, e.bytes);
-            { const double cols = (double)p.H * p.W * p.nbatch; e.flops += 2.0 * p.cg * p.nfeat * cols; e.bytes += 2.0 * p.cg * p.nfeat + 2.0 * p.nfeat * cols; }
-            e.dH = p.H; e.dW = p.W; e.dCin = p.cg; e.dCout = p.nfeat;
-            e.e0 = g_prof.get(); e.e1 = g_prof.get();
-            HIPC(hipEventRecord(e.e0, st));
-            hipLaunchKernelGGL(conv_ws128_kernel, dim3(grid), dim3(CvWs128::THREADS), CvWs128::LDS, st, p);
-            HIPC(hipEventRecord(e.e1, st));
-            g_prof.entries.push_back(e);
-        } else {
-            hipLaunchKernelGGL(conv_ws128_kernel, dim3(grid), dim3(CvWs128::THREADS), CvWs128::LDS, st, p);
-        }
-        HIPC(hipGetLastError());
-        return did_res;
-    }
+    if (!env().no_atile && halo && !upph && !did_res && tm_run == w.TM && w.Atile && w.ntaps == 9) p.A_tiled = w.Atile;
     if (halo && !did_res && !p.out_nchw && w.cout % 8 == 0) {
         const int taps = upph ? 4 : 9, tps = 256 / tm_run;
         const int ks = choose_ksplit(p.nbatch * p.tiles * p.rowtiles, cin / HC_BK, (taps + tps - 1) / tps,
@@ -755,70 +744,57 @@ static bool run_conv(const ConvW& w, const Act& x0, const Act* x1, Act& y, int m
     }
     // 128-row tiles have no registers for a second accumulator set: the block's 1x1 res_conv rides in the same LAUNCH instead,
     // as extra workgroups behind the 3x3 ones (same input, one tap) that fill the last, partly empty round of the grid
-    static const bool tail_res = !getenv("UCDIR_NO_TAIL_RES");
-    if (halo && !upph && !did_res && res_out && wres && tail_res && !p.out_nchw && wres->ntaps == 1 &&
-        wres->rows_pad >= p.rowtiles * tm_run) {
+    if (halo && !upph && !did_res && c.res_out && c.wres && !env().no_tail_res && !p.out_nchw && c.wres->ntaps == 1 &&
+        c.wres->rows_pad >= p.rowtiles * tm_run) {
         p.alt_blocks = p.nbatch * p.tiles * p.rowtiles;
-        p.alt_A = wres->A; p.alt_a_ld = wres->Kpad; p.bias2 = wres->bias;
-        p.out2 = res_out->p; p.out2_bstride = res_out->bstride(); p.out2_ld = res_out->C;
+        p.alt_A = c.wres->A; p.alt_a_ld = c.wres->Kpad; p.bias2 = c.wres->bias;
+        p.out2 = c.res_out->p; p.out2_bstride = c.res_out->bstride(); p.out2_ld = c.res_out->C;
         did_res = true;
     }
+    ConvKind kind = !halo ? ConvKind::CGEMM : tm_run == 128 ? ConvKind::HALO128 : dual ? ConvKind::HALO64_DUAL : ConvKind::HALO64;
+    // 128 -> 64 with the res_conv fused, on 8 x 16 tiles: persistent kernel with one wave per SIMD (conv_ws128.hip.h)
+    if (!env().no_conv_ws128 && dual && w.Aws128 && cin == 128 && x0.C == 64 && x1 && x1->C == 64 && !c.res && !p.out_nchw && y.H % 8 == 0 && y.W % 16 == 0 &&
+        y.C == 64 && (g_persist_grid > 0 || (long long)y.B * (y.H / 8) * (y.W / 16) >= 4LL * num_cus()))
+        kind = ConvKind::WS128;
     // 64 -> 64 on 16 x 16 tiles: persistent weight-stationary kernel (conv_ws.hip.h); UCDIR_NO_CONV_WS falls back
-    static const bool use_cws = !getenv("UCDIR_NO_CONV_WS");
-    if (use_cws && halo && !upph && !did_res && !dual && w.Aws && !x1 && !res && !p.out_nchw && p.ksplit <= 1 && !p.alt_blocks &&
-        y.H % 16 == 0 && y.W % 16 == 0 && x0.C == 64 && y.C == 64 &&
-        (g_persist_grid > 0 || (long long)y.B * (y.H / 16) * (y.W / 16) >= 4LL * num_cus())) {
-        p.A = w.Aws; p.th = 16; p.tw = 16; p.tiles_x = y.W / 16; p.tiles_y = y.H / 16;
-        const int ntiles = y.B * p.tiles_x * p.tiles_y, ncu = num_cus();
-        const int grid = ntiles < ncu ? ntiles : ncu;
-#ifdef UCDIR_TIMING
-        {
-            static unsigned long long* dbgbuf = nullptr;
-            if (!dbgbuf) HIPC(hipMalloc((void**)&dbgbuf, 512 * 8));
-            HIPC(hipMemset(dbgbuf, 0, 512 * 8));
-            p.dbg = dbgbuf;
-            hipLaunchKernelGGL(conv_ws_kernel, dim3(grid), dim3(HC_THREADS), CvWs::LDS, st, p);
-            unsigned long long h[512];
-            HIPC(hipStreamSynchronize(st));
-            HIPC(hipMemcpy(h, dbgbuf, sizeof(h), hipMemcpyDeviceToHost));
-            for (int w = 0; w < 2; ++w) {
-                const int n = (int)h[w * 256 + 255];
-                fprintf(stderr, "CONV_WS TIMING %s n=%d:", w ? "late" : "early", n);
-                for (int i = 1; i < n && i < 255; ++i) fprintf(stderr, " %llu", h[w * 256 + i] - h[w * 256 + i - 1]);
-                fprintf(stderr, "\n");
-            }
-            return did_res;
+    else if (!env().no_conv_ws && halo && !upph && !did_res && w.Aws && !x1 && !c.res && !p.out_nchw && p.ksplit <= 1 && !p.alt_blocks &&
+             y.H % 16 == 0 && y.W % 16 == 0 && x0.C == 64 && y.C == 64 &&
+             (g_persist_grid > 0 || (long long)y.B * (y.H / 16) * (y.W / 16) >= 4LL * num_cus()))
+        kind = ConvKind::WS;
+
+    // ---- launch it ---------------------------------------------------------------------------------------------------------------
+    switch (kind) {
+        case ConvKind::WS128: {
+            p.A = w.Aws128; p.alt_A = w.Aws128 + (size_t)2 * 72 * 2 * 32 * 8;
+            p.th = 8; p.tw = 16; p.tiles_x = y.W / 16; p.tiles_y = y.H / 8;
+            const int ntiles = y.B * p.tiles_x * p.tiles_y, ncu = num_cus();
+            const int grid = ntiles < ncu ? ntiles : ncu;
+            ProfEntry e = gemm_entry(KEY_CONV_WS128, p, EPI_STD, p.cg);
+            add_res_rider(e, p);
+            StampDump sd(st, STAMPS_256); p.dbg = sd.dbg();
+            bracket(e, st, [&] { hipLaunchKernelGGL(conv_ws128_kernel, dim3(grid), dim3(CvWs128::THREADS), CvWs128::LDS, st, p); });
+            sd.print([](int, int n) { fprintf(stderr, "CONV_WS128 TIMING n=%d:", n); });
+            break;
         }
-#endif
-        if (g_prof.on) {
-            ProfEntry e; e.key = 23; gemm_work(p, EPI_STD, e.flops, e.bytes);
-            e.dH = p.H; e.dW = p.W; e.dCin = p.cg; e.dCout = p.nfeat;
-            e.e0 = g_prof.get(); e.e1 = g_prof.get();
-            HIPC(hipEventRecord(e.e0, st));
-            hipLaunchKernelGGL(conv_ws_kernel, dim3(grid), dim3(HC_THREADS), CvWs::LDS, st, p);
-            HIPC(hipEventRecord(e.e1, st));
-            g_prof.entries.push_back(e);
-        } else {
-            hipLaunchKernelGGL(conv_ws_kernel, dim3(grid), dim3(HC_THREADS), CvWs::LDS, st, p);
+        case ConvKind::WS: {
+            p.A = w.Aws; p.th = 16; p.tw = 16; p.tiles_x = y.W / 16; p.tiles_y = y.H / 16;
+            const int ntiles = y.B * p.tiles_x * p.tiles_y, ncu = num_cus();
+            const int grid = ntiles < ncu ? ntiles : ncu;
+            StampDump sd(st, STAMPS_CONV_WS); p.dbg = sd.dbg();
+            bracket(gemm_entry(KEY_CONV_WS, p, EPI_STD, p.cg), st, [&] { hipLaunchKernelGGL(conv_ws_kernel, dim3(grid), dim3(HC_THREADS), CvWs::LDS, st, p); });
+            sd.print([](int win, int n) { fprintf(stderr, "CONV_WS TIMING %s n=%d:", win ? "late" : "early", n); });
+            break;
         }
-        HIPC(hipGetLastError());
-        return did_res;
+        case ConvKind::HALO128: launch_halo<128>(p, st); break;
+        case ConvKind::HALO64_DUAL: launch_halo<64, true>(p, st); break;
+        case ConvKind::HALO64: launch_halo<64>(p, st); break;
+        case ConvKind::CGEMM: launch_cgemm(p, w.TM, EPI_STD, st); break;
     }
-    if (halo) { if (tm_run == 128) launch_halo<128>(p, st); else if (dual) launch_halo<64, true>(p, st); else launch_halo<64>(p, st); }
-    else launch_cgemm(p, w.TM, EPI_STD, st);
-#ifdef UCDIR_TIMING
-    if (halo) {
-        unsigned long long h[256];
-        HIPC(hipStreamSynchronize(st));
-        HIPC(hipMemcpy(h, dbgbuf, sizeof(h), hipMemcpyDeviceToHost));
-        const int n = (int)h[255];
-        fprintf(stderr, "TIMING n=%d:", n);
-        for (int i = 1; i < n && i < 255; ++i) fprintf(stderr, " %llu", h[i] - h[i - 1]);
-        fprintf(stderr, "\n");
-    }
-#endif
     return did_res;
 }
+
+// The kernels of the AKGM tail.  WS*: persistent, one workgroup per CU walks a range of tiles; the others one workgroup per tile
+enum class AkgmKind { WS64_4, WS64_2, WS32, WS, WS16, PRE, HALO_ATTLDS, HALO_STAGE };
 
 // halo-tile AKGM kernel (akgm_halo.hip.h): 8 / 16 / 32 / 64 channels per group
 // tcbuf: caller-owned fold-table scratch of at least y.B * (9 * 8 * C + 2) floats (the context plans one; nothing is
@@ -828,8 +804,7 @@ static void run_akgm_halo(const AkgmW& w, const Act& h1, const float* G, const f
     // (A persistent variant - one workgroup walking a range of tiles with the weights loaded once - was built and measured
     // in round 2: 128 registers per wave do not hold the tile-loop state next to 64 accumulators, hipcc spilled 14-39
     // registers with scratch reloads inside the loop, and the launch went from 238 to 306 us.  See DESIGN.md.)
-    static const bool use_pre = !getenv("UCDIR_NO_PRE");
-    const bool pre = use_pre && w.Apre != nullptr && w.cg == 8;
+    const bool pre = !env().no_pre && w.Apre != nullptr && w.cg == 8;
     require(tcbuf != nullptr, "AKGM: no fold-table scratch");
     const double inv_cnt = 1.0 / ((double)w.C * h1.H * h1.W);
     float* msbuf = tcbuf + (size_t)y.B * 9 * 8 * w.C;                    // (mean, rstd) per sample, behind the table
@@ -854,36 +829,39 @@ static void run_akgm_halo(const AkgmW& w, const Act& h1, const float* G, const f
         p.usplit = choose_usplit(nblk);
         nblk *= p.usplit;
     }
-    p.dbg = nullptr;
-    static const bool use_attlds = !getenv("UCDIR_NO_ATTLDS");
-    const bool att_lds = use_attlds && (w.cg == 16 || w.cg == 32);     // one halo chunk per workgroup: second buffer free
+    // the persistent kernels form their fold constants themselves (27 launches of ~5 us less per B = 16 forward; UCDIR_NO_OWNTC=1: akgm_tc_kernel for all)
+    // (round 5, late: the one-shot kernels of the B = 1 path as well - their Tc slices are formed where the LDS-DMA from akgm_tc_kernel's table was issued)
+    p.own_tc = !env().no_owntc && w.Tbb != nullptr;
+    p.Tbb = w.Tbb; p.Tgt = w.Tg;
+
+    // ---- which kernel: the one-shot kernel of this group size, unless a persistent one engages (of two that do, the later one below) ----
+    // (halo<att-lds>: one halo chunk per workgroup at 16 / 32 channels per group, second buffer free)
+    AkgmKind kind = pre ? AkgmKind::PRE : (!env().no_attlds && (w.cg == 16 || w.cg == 32)) ? AkgmKind::HALO_ATTLDS : AkgmKind::HALO_STAGE;
     // persistent weight-stationary kernel (akgm_ws.hip.h): one workgroup per CU walks a range of tiles; UCDIR_NO_WS falls back
-    static const bool use_ws = !getenv("UCDIR_NO_WS");
+    const bool use_ws = !env().no_ws;
     // (persistent kernels pay from ~4 tiles per CU on: at B = 1, 256^2 - 324 tiles, one or two per workgroup - the one-shot
     // kernels are 5 % faster per step; the forced grid of the tests bypasses the threshold)
-    const bool ws = pre && use_ws && w.C == 64 && y.H % 16 == 0 && y.W % 16 == 0 && p.th == 16 && p.tw == 16 &&
-                    (g_persist_grid > 0 || (long long)y.B * p.tiles_x * p.tiles_y >= 4LL * num_cus());
+    if (pre && use_ws && w.C == 64 && y.H % 16 == 0 && y.W % 16 == 0 && p.th == 16 && p.tw == 16 &&
+        (g_persist_grid > 0 || (long long)y.B * p.tiles_x * p.tiles_y >= 4LL * num_cus()))
+        kind = AkgmKind::WS;
     // 16 channels per group (C = 128): the same kernel, one 64-channel plane per workgroup
-    static const bool use_ws16 = !getenv("UCDIR_NO_WS16");
-    const bool ws16 = use_ws && use_ws16 && w.Apre != nullptr && w.cg == 16 && w.C == 128 && y.H % 16 == 0 && y.W % 16 == 0 &&
-                      (g_persist_grid > 0 || (long long)y.B * (y.H / 16) * (y.W / 16) * 2 >= 4LL * num_cus());
-    if (ws16) { p.A = w.Apre; p.th = 16; p.tw = 16; p.tiles_x = y.W / 16; p.tiles_y = y.H / 16; }
+    if (use_ws && !env().no_ws16 && w.Apre != nullptr && w.cg == 16 && w.C == 128 && y.H % 16 == 0 && y.W % 16 == 0 &&
+        (g_persist_grid > 0 || (long long)y.B * (y.H / 16) * (y.W / 16) * 2 >= 4LL * num_cus()))
+        kind = AkgmKind::WS16;
     // 32 channels per group (C = 256): one group per workgroup, TH x 8 tiles (akgm_ws32.hip.h)
-    static const bool use_ws32 = !getenv("UCDIR_NO_WS32");
     int th32 = 0;
     for (int cand : {32, 24, 16, 8}) if (y.H % cand == 0) { th32 = cand; break; }
     // (ucdir_debug_flag("wsb", 1): the block kernel also at 8 / 16 channels per group instead of akgm_ws_kernel - tests)
     const bool wsb_all = g_wsb > 0;
     const int nb32 = w.C / 32;
-    const bool ws32 = use_ws && use_ws32 && w.Aws32 != nullptr && (w.cg == 32 || (wsb_all && (w.cg == 16 || w.cg == 8))) && w.C == 8 * w.cg && th32 > 0 && y.W % 8 == 0 &&
-                      (g_persist_grid > 0 || (long long)y.B * (y.H / th32) * (y.W / 8) * nb32 >= 4LL * num_cus());
-    if (ws32) { p.A = w.Aws32; p.th = th32; p.tw = 8; p.tiles_x = y.W / 8; p.tiles_y = y.H / th32; }
+    if (use_ws && !env().no_ws32 && w.Aws32 != nullptr && (w.cg == 32 || (wsb_all && (w.cg == 16 || w.cg == 8))) && w.C == 8 * w.cg && th32 > 0 && y.W % 8 == 0 &&
+        (g_persist_grid > 0 || (long long)y.B * (y.H / th32) * (y.W / 8) * nb32 >= 4LL * num_cus()))
+        kind = AkgmKind::WS32;
     // 64 channels per group (C = 512: the 36^2 / 18^2 levels), akgm_ws64.hip.h: half a group per workgroup of eight waves, one per CU, the tile's
     // memory chores on waves 0 - 3; linear tiles of 64 | 128 positions of the zero-bordered plane; roles x (resident workgroups / roles) tile
     // ranges.  From two tiles per range on (B = 1 keeps the one-shot kernel and its unit split); UCDIR_NO_WS64 falls back to akgm_halo_stage_kernel
-    static const bool use_ws64 = !getenv("UCDIR_NO_WS64");
-    int npt64 = 0, tps64 = 0, grid64 = 0, lds64 = 0;
-    if (use_ws && use_ws64 && w.Aws64 != nullptr && w.cg == 64 && w.C == 512 && y.H >= 2 && (y.H + 2) * (y.W + 2) < 32768) {
+    int tps64 = 0, grid64 = 0, hpos64 = 0;
+    if (use_ws && !env().no_ws64 && w.Aws64 != nullptr && w.cg == 64 && w.C == 512 && y.H >= 2 && (y.H + 2) * (y.W + 2) < 32768) {
         const int nrole = 128 / AkWs64::NW;
         grid64 = num_cus() / nrole * nrole; if (grid64 < nrole) grid64 = nrole;
         const int span = (y.H - 1) * (y.W + 2) + y.W, nslots = grid64 / nrole;
@@ -896,76 +874,55 @@ static void run_akgm_halo(const AkgmW& w, const Act& h1, const float* G, const f
             // the one-shot kernel wins: B = 1 at 52^2 - the DDPM.test geometry - 41 vs 25.5 us, B = 2 at 36^2 30 vs 25, B = 1 at 64^2 48 vs 28.5)
             const bool enough = cand == 4 ? (long long)y.B * tps >= 4LL * nslots : 2LL * y.B * span >= 3LL * nslots * hpos;
             if (g_persist_grid > 0 || enough) {
-                npt64 = cand; tps64 = tps;
-                lds64 = AkWs64::lds(hpos);
-                p.tw = AkWs64::HBYTES(hpos);
+                kind = cand == 4 ? AkgmKind::WS64_4 : AkgmKind::WS64_2;
+                tps64 = tps; hpos64 = hpos;
                 break;
             }
         }
     }
-    const bool ws64 = npt64 > 0;
-    if (ws64) { p.A = w.Aws64; p.th = npt64; p.tiles_x = tps64; p.tiles_y = 1; }
-    // the persistent kernels form their fold constants themselves (27 launches of ~5 us less per B = 16 forward; UCDIR_NO_OWNTC=1: akgm_tc_kernel for all)
-    static const bool use_owntc = !getenv("UCDIR_NO_OWNTC");
-    // (round 5, late: the one-shot kernels of the B = 1 path as well - their Tc slices are formed where the LDS-DMA from akgm_tc_kernel's table was issued)
-    p.own_tc = use_owntc && w.Tbb != nullptr;
-    p.Tbb = w.Tbb; p.Tgt = w.Tg;
-    if (!p.own_tc)
-        hipLaunchKernelGGL(akgm_tc_kernel, dim3(9 * ((8 * w.C + 1023) / 1024), y.B), dim3(256), 0, st, h1.stats, inv_cnt, w.bias, w.Tb, w.Tg, 8 * w.C, tcbuf, msbuf);
-    auto launch = [&]() {
-        if (ws64) {
-            if (npt64 == 4) hipLaunchKernelGGL((akgm_ws64_kernel<4, 8, true>), dim3(grid64), dim3(512), lds64, st, p);
-            else hipLaunchKernelGGL((akgm_ws64_kernel<2, 8, true>), dim3(grid64), dim3(512), lds64, st, p);
-        } else if (ws32) {
+
+    // ---- its fields, grid and profiler key, then the launch -----------------------------------------------------------------------------
+    void (*kernel)(AkgmHP) = akgm_halo_stage_kernel;
+    int key = KEY_AKGM_HALO, grid = nblk, threads = HC_THREADS, lds = AH_LDS;
+    switch (kind) {
+        case AkgmKind::WS64_4: case AkgmKind::WS64_2:
+            p.A = w.Aws64; p.th = kind == AkgmKind::WS64_4 ? 4 : 2; p.tw = AkWs64::HBYTES(hpos64); p.tiles_x = tps64; p.tiles_y = 1;
+            kernel = kind == AkgmKind::WS64_4 ? akgm_ws64_kernel<4, 8, true> : akgm_ws64_kernel<2, 8, true>;
+            key = KEY_AKGM_WS64; grid = grid64; threads = 512; lds = AkWs64::lds(hpos64);
+            break;
+        case AkgmKind::WS32: {
+            p.A = w.Aws32; p.th = th32; p.tw = 8; p.tiles_x = y.W / 8; p.tiles_y = y.H / th32;
             const int ntiles = y.B * p.tiles_x * p.tiles_y;
             int ncu = num_cus() / nb32 * nb32; if (ncu < nb32) ncu = nb32;
-            const int grid = nb32 * ntiles < ncu ? nb32 * ntiles : ncu;      // one workgroup per 32-feature block per tile range
-            if (w.cg == 32) hipLaunchKernelGGL(akgm_ws32_kernel<32>, dim3(grid), dim3(HC_THREADS), AkWs32::LDS, st, p);
-            else if (w.cg == 16) hipLaunchKernelGGL(akgm_ws32_kernel<16>, dim3(grid), dim3(HC_THREADS), AkWs32::LDS, st, p);
-            else hipLaunchKernelGGL(akgm_ws32_kernel<8>, dim3(grid), dim3(HC_THREADS), AkWs32::LDS, st, p);
-        } else if (ws) {
+            grid = nb32 * ntiles < ncu ? nb32 * ntiles : ncu;                // one workgroup per 32-feature block per tile range
+            kernel = w.cg == 32 ? akgm_ws32_kernel<32> : w.cg == 16 ? akgm_ws32_kernel<16> : akgm_ws32_kernel<8>;
+            key = KEY_AKGM_WS32; lds = AkWs32::LDS;
+            break;
+        }
+        case AkgmKind::WS: {
             const int ntiles = y.B * p.tiles_x * p.tiles_y, ncu = num_cus();
-            const int grid = ntiles < ncu ? ntiles : ncu;
-            hipLaunchKernelGGL(akgm_ws_kernel<8>, dim3(grid), dim3(HC_THREADS), AkWs::LDS, st, p);
-        } else if (ws16) {
+            grid = ntiles < ncu ? ntiles : ncu;
+            kernel = akgm_ws_kernel<8>; key = KEY_AKGM_WS; lds = AkWs::LDS;
+            break;
+        }
+        case AkgmKind::WS16: {
+            p.A = w.Apre; p.th = 16; p.tw = 16; p.tiles_x = y.W / 16; p.tiles_y = y.H / 16;
             int ncu = num_cus() & ~1; if (ncu < 2) ncu = 2;                  // persist_grid = 1 must not give an empty grid (round-3 advice)
             const int ntiles = y.B * p.tiles_x * p.tiles_y;
-            const int grid = 2 * ntiles < ncu ? 2 * ntiles : ncu;            // workgroup pairs: (tile range, channel plane)
-            hipLaunchKernelGGL(akgm_ws_kernel<16>, dim3(grid), dim3(HC_THREADS), AkWs::LDS, st, p);
-        } else if (pre) {
-            hipLaunchKernelGGL(akgm_pre_kernel<8>, dim3(nblk), dim3(HC_THREADS), AkPre<8>::LDS, st, p);
-        } else if (att_lds) hipLaunchKernelGGL(akgm_halo_kernel<true>, dim3(nblk), dim3(HC_THREADS), AH_LDS, st, p);
-        else hipLaunchKernelGGL(akgm_halo_stage_kernel, dim3(nblk), dim3(HC_THREADS), AH_LDS, st, p);
-    };
-#ifdef UCDIR_TIMING
-    static unsigned long long* dbgbuf = nullptr;
-    if (!dbgbuf) HIPC(hipMalloc((void**)&dbgbuf, 256 * 8));
-    HIPC(hipMemset(dbgbuf, 0, 256 * 8));
-    p.dbg = dbgbuf;
-    launch();
-    {
-        unsigned long long h[256];
-        HIPC(hipStreamSynchronize(st));
-        HIPC(hipMemcpy(h, dbgbuf, sizeof(h), hipMemcpyDeviceToHost));
-        const int n = (int)h[255];
-        fprintf(stderr, "AKGM TIMING cg=%d n=%d:", w.cg, n);
-        for (int i = 1; i < n && i < 255; ++i) fprintf(stderr, " %llu", h[i] - h[i - 1]);
-        fprintf(stderr, "\n");
+            grid = 2 * ntiles < ncu ? 2 * ntiles : ncu;                      // workgroup pairs: (tile range, channel plane)
+            kernel = akgm_ws_kernel<16>; key = KEY_AKGM_WS16; lds = AkWs::LDS;
+            break;
+        }
+        case AkgmKind::PRE: kernel = akgm_pre_kernel<8>; key = KEY_AKGM_PRE; lds = AkPre<8>::LDS; break;
+        case AkgmKind::HALO_ATTLDS: kernel = akgm_halo_kernel<true>; break;
+        case AkgmKind::HALO_STAGE: break;
     }
-#endif
-    if (g_prof.on) {
-        ProfEntry e; e.key = ws64 ? 116 : ws32 ? 115 : (ws ? 113 : (ws16 ? 114 : (pre ? 112 : 111))); e.flops = 2.0 * 9 * w.C * (double)w.C * y.H * y.W * y.B;
-        e.bytes = (3.0 * w.C * 2 + 32) * (double)y.H * y.W * y.B + 9.0 * w.C * w.C * 2;
-        e.dH = y.H; e.dW = y.W; e.dCin = w.C; e.dCout = w.C;
-        e.e0 = g_prof.get(); e.e1 = g_prof.get();
-        HIPC(hipEventRecord(e.e0, st));
-        launch();
-        HIPC(hipEventRecord(e.e1, st));
-        g_prof.entries.push_back(e);
-    } else {
-        launch();
-    }
-    HIPC(hipGetLastError());
+    if (!p.own_tc)
+        hipLaunchKernelGGL(akgm_tc_kernel, dim3(9 * ((8 * w.C + 1023) / 1024), y.B), dim3(256), 0, st, h1.stats, inv_cnt, w.bias, w.Tb, w.Tg, 8 * w.C, tcbuf, msbuf);
+    const ProfEntry e{key, 2.0 * 9 * w.C * (double)w.C * y.H * y.W * y.B, (3.0 * w.C * 2 + 32) * (double)y.H * y.W * y.B + 9.0 * w.C * w.C * 2, y.H, y.W, w.C, w.C};
+    StampDump sd(st, STAMPS_256); p.dbg = sd.dbg();
+    bracket(e, st, [&] { hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), lds, st, p); });
+    sd.print([&](int, int n) { fprintf(stderr, "AKGM TIMING cg=%d n=%d:", w.cg, n); });
 }
 
 // AKGM tail of a block: y = swish(sum_s spdyconv(GN2(h1))[c,s] * G[s] * attw[s]) + res
@@ -1009,8 +966,7 @@ struct AttnBufs {
 
 static std::atomic<int> g_flash{-1};          // -1: environment (UCDIR_NO_FLASH), 0 / 1: ucdir_debug_flag("flash", v)
 static bool flash_ok(int C) {
-    static const bool env_on = !getenv("UCDIR_NO_FLASH");
-    const bool on = g_flash < 0 ? env_on : g_flash != 0;
+    const bool on = g_flash < 0 ? !env().no_flash : g_flash != 0;
     return on && C % 128 == 0 && C <= 512;
 }
 
@@ -1055,8 +1011,7 @@ static void run_attention(const ConvW& wqkv, const ConvW& wout, const Act& x, Ac
     require(C % 128 == 0, "attention: channels must be a multiple of 128");
     require((size_t)N <= (size_t)a.N && C == a.C && B <= a.B, "attention buffers too small");
     // 1 + 2. q, k -> qkv, v' -> V't straight from one persistent weight-stationary GEMM (qkv_ws.hip.h); UCDIR_NO_QKV_WS falls back
-    static const bool use_qkv_ws = !getenv("UCDIR_NO_QKV_WS");
-    const bool qws = use_qkv_ws && wqkv.Aqkv && !a.half && (C == 256 || C == 512);
+    const bool qws = !env().no_qkv_ws && wqkv.Aqkv && !a.half && (C == 256 || C == 512);
     if (qws) {
         QkvP q;
         q.A = wqkv.Aqkv; q.x = x.p; q.x_bstride = x.bstride();
@@ -1067,20 +1022,11 @@ static void run_attention(const ConvW& wqkv, const ConvW& wout, const Act& x, Ac
         q.vt = a.Vt; q.vt_bstride = (long long)C * Npad; q.Npad = Npad;
         const int units = q.rowtiles * B * q.tps, ncu = num_cus();
         const int grid = units < ncu ? units : ncu;
-        auto launch = [&]() {
+        const ProfEntry e{KEY_QKV_WS, 2.0 * 3 * C * (double)C * N * B, ((double)N * C * 2 + (double)N * 3 * C * 2) * B + 3.0 * C * C * 2, x.H, x.W, C, 3 * C};
+        bracket(e, st, [&] {
             if (C == 512) hipLaunchKernelGGL(qkv_ws_kernel<512>, dim3(grid), dim3(HC_THREADS), QkvWs::LDS, st, q);
             else hipLaunchKernelGGL(qkv_ws_kernel<256>, dim3(grid), dim3(HC_THREADS), QkvWs::LDS, st, q);
-        };
-        if (g_prof.on) {
-            ProfEntry e; e.key = 105; e.flops = 2.0 * 3 * C * (double)C * N * B; e.bytes = ((double)N * C * 2 + (double)N * 3 * C * 2) * B + 3.0 * C * C * 2;
-            e.dH = x.H; e.dW = x.W; e.dCin = C; e.dCout = 3 * C;
-            e.e0 = g_prof.get(); e.e1 = g_prof.get();
-            HIPC(hipEventRecord(e.e0, st));
-            launch();
-            HIPC(hipEventRecord(e.e1, st));
-            g_prof.entries.push_back(e);
-        } else launch();
-        HIPC(hipGetLastError());
+        });
     } else {
     // 1. q,k,v = conv1x1(GN(x))   (GroupNorm folded; output compact [B][N][3C])
     {
@@ -1112,18 +1058,13 @@ static void run_attention(const ConvW& wqkv, const ConvW& wout, const Act& x, Ac
         f.res = x.p; f.res_bstride = x.bstride(); f.out = y.p; f.out_bstride = y.bstride();
         f.stats_out = y.stats;
         f.nq = (N + FA_BQ - 1) / FA_BQ;
-        f.dbg = nullptr;
-#ifdef UCDIR_TIMING
-        static unsigned long long* fdbg = nullptr;
-        if (!fdbg) HIPC(hipMalloc((void**)&fdbg, 256 * 8));
-        HIPC(hipMemset(fdbg, 0, 256 * 8));
-        f.dbg = fdbg;
-#endif
+        StampDump sd(st, STAMPS_256); f.dbg = sd.dbg();
         const dim3 grid((unsigned)(B * f.nq));
         // flash_attn2_kernel: 128 queries per workgroup, 64-key tiles, all eight waves in one phase, two barriers per tile, every fragment read of
         // the S and PV phases as inline asm with counted lgkmcnt
         const size_t lds = fa_lds_bytes(C);
-        auto launch = [&]() {
+        const ProfEntry e{a.half ? KEY_FLASH_F16 : KEY_FLASH, 4.0 * (double)N * N * C * B, ((double)N * 3 * C * 2 + 2.0 * N * C * 2) * B, x.H, x.W, C, C};
+        bracket(e, st, [&] {
             switch (C / 128 * 2 + (a.half ? 1 : 0)) {
                 case 2: hipLaunchKernelGGL((flash_attn2_kernel<1, false>), grid, dim3(FA_THREADS), lds, st, f); break;
                 case 3: hipLaunchKernelGGL((flash_attn2_kernel<1, true>), grid, dim3(FA_THREADS), lds, st, f); break;
@@ -1134,29 +1075,9 @@ static void run_attention(const ConvW& wqkv, const ConvW& wout, const Act& x, Ac
                 case 8: hipLaunchKernelGGL((flash_attn2_kernel<4, false>), grid, dim3(FA_THREADS), lds, st, f); break;
                 default: hipLaunchKernelGGL((flash_attn2_kernel<4, true>), grid, dim3(FA_THREADS), lds, st, f); break;
             }
-        };
-        if (g_prof.on) {
-            ProfEntry e; e.key = 130 + (a.half ? 1 : 0); e.flops = 4.0 * (double)N * N * C * B;
-            e.bytes = ((double)N * 3 * C * 2 + 2.0 * N * C * 2) * B;
-            e.dH = x.H; e.dW = x.W; e.dCin = C; e.dCout = C;
-            e.e0 = g_prof.get(); e.e1 = g_prof.get();
-            HIPC(hipEventRecord(e.e0, st));
-            launch();
-            HIPC(hipEventRecord(e.e1, st));
-            g_prof.entries.push_back(e);
-        } else launch();
-        HIPC(hipGetLastError());
-#ifdef UCDIR_TIMING
-        {   // per-tile phase anatomy of one wave: deltas between the six stamps of tiles 4 .. 7 (steady state)
-            unsigned long long h[256];
-            HIPC(hipStreamSynchronize(st));
-            HIPC(hipMemcpy(h, fdbg, sizeof(h), hipMemcpyDeviceToHost));
-            const int n = (int)h[255];
-            fprintf(stderr, "FLASH TIMING N=%d C=%d B=%d stamps=%d:", N, C, B, n);
-            for (int i = 1; i < n && i < 255; ++i) fprintf(stderr, " %llu", h[i] - h[i - 1]);
-            fprintf(stderr, "\n");
-        }
-#endif
+        });
+        // per-tile phase anatomy of one wave: deltas between the six stamps of tiles 4 .. 7 (steady state)
+        sd.print([&](int, int n) { fprintf(stderr, "FLASH TIMING N=%d C=%d B=%d stamps=%d:", N, C, B, n); });
         return;
     }
     // 3. S[i][j] = q_i . k_j / sqrt(C)   (rows = keys j, cols = queries i)
@@ -1459,8 +1380,7 @@ static void plan_shapes(ucdir_ctx* c, int B, int H, int W, int pad_mode) {
     else { c->Hc = H; c->Wc = W; }
     const int nlev = c->cfg.n_mults;
     require(c->Hc % (1 << (nlev - 1)) == 0 && c->Wc % (1 << (nlev - 1)) == 0, "compute size must be divisible by 2^(levels-1)");
-    static const bool keep_env = getenv("UCDIR_KEEP_ACTS") != nullptr;
-    c->acts_reused = !keep_env && (long long)c->Hc * c->Wc > 512LL * 512;
+    c->acts_reused = !env().keep_acts && (long long)c->Hc * c->Wc > 512LL * 512;
     ActPlanner ap{c->apool, B, c->acts_reused, {}};
     int maxN = 0, attC = 0;
     double fl = 0;
@@ -1509,8 +1429,7 @@ static void plan_shapes(ucdir_ctx* c, int B, int H, int W, int pad_mode) {
     fl += 2.0 * 9 * c->cfg.inner_channel * c->cfg.channel_mults[0] * c->cfg.out_channel * c->Hc * c->Wc;
     c->flops = fl * B;
     c->fin_act = Act();
-    static const bool unfused_final = getenv("UCDIR_NO_FUSED_FINAL") != nullptr;
-    if (!c->fin_w || unfused_final) c->fin_act = make_act(c->apool, B, c->Hc, c->Wc, c->cfg.inner_channel * c->cfg.channel_mults[0], false);
+    if (!c->fin_w || env().no_fused_final) c->fin_act = make_act(c->apool, B, c->Hc, c->Wc, c->cfg.inner_channel * c->cfg.channel_mults[0], false);
     if (maxN > 0) alloc_attn(c->apool, c->attn, B, maxN, attC, c->cfg.attn_fp16 != 0);
     c->attw = (float*)c->apool.alloc((size_t)c->nblocks * B * 8 * sizeof(float));
     {
@@ -1547,16 +1466,16 @@ static void forward(ucdir_ctx* c, const float* cond, const float* xt, const floa
                                c->Hc, c->Wc, d.cout, tx, w.stem_w, r.out.p, r.out.stats, tx * ty, d.cout / 64, B);
             HIPC(hipGetLastError());
         } else if (d.kind == "down") {
-            run_conv(w.conv, *cur, nullptr, r.out, COLS_DOWN, 0, nullptr, true, st);
+            run_conv(w.conv, COLS_DOWN, {*cur, nullptr, r.out, 0, nullptr, true}, st);
         } else if (d.kind == "up") {
-            run_conv(w.conv, *cur, nullptr, r.out, COLS_UP, 0, nullptr, true, st);
+            run_conv(w.conv, COLS_UP, {*cur, nullptr, r.out, 0, nullptr, true}, st);
         } else {
             const Act* x0 = cur; const Act* x1 = nullptr;
             if (d.skip_c) { x1 = skips.back(); skips.pop_back(); require(x1->C == d.skip_c, "skip channel mismatch"); }
             // h1 = swish(conv1(GN1(cat[x0,x1])))
-            const bool res_done = run_conv(w.conv, *x0, x1, r.h1, COLS_S1, 1, nullptr, true, st, nullptr, 0, 0, w.has_res ? &r.res : nullptr, w.has_res ? &w.resconv : nullptr);
+            const bool res_done = run_conv(w.conv, COLS_S1, {*x0, x1, r.h1, 1, nullptr, true, w.has_res ? &r.res : nullptr, w.has_res ? &w.resconv : nullptr}, st);
             const Act* res = x0;
-            if (w.has_res) { if (!res_done) run_conv(w.resconv, *x0, x1, r.res, COLS_S1, 0, nullptr, false, st); res = &r.res; }
+            if (w.has_res) { if (!res_done) run_conv(w.resconv, COLS_S1, {*x0, x1, r.res, 0, nullptr, false}, st); res = &r.res; }
             Act& bo = d.attn ? r.bo : r.out;
             run_akgm(w.sp, r.h1, r.G, c->attw + (size_t)w.block_index * B * 8, *res, bo, c->tcbuf, st);
             if (d.attn) run_attention(w.qkv, w.outp, bo, r.out, c->attn, st);
@@ -1568,8 +1487,7 @@ static void forward(ucdir_ctx* c, const float* cond, const float* xt, const floa
     // (out_channel > 4) take the activation pass + the MFMA conv
     {
         const int C = cur->C, co = c->cfg.out_channel;
-        static const bool fused = !getenv("UCDIR_NO_FUSED_FINAL");
-        if (fused && c->fin_w) {
+        if (!env().no_fused_final && c->fin_w) {
             const int tiles = ((c->Wc + 15) / 16) * ((c->Hc + 15) / 16) * B;
             const dim3 grid(tiles < 3 * num_cus() ? tiles : 3 * num_cus());   // persistent: three resident workgroups per CU walk the tiles
             const size_t lds = (size_t)324 * 80 + (size_t)9 * (C / 32) * 1024 + (size_t)8 * C + (size_t)8 * B;
@@ -1582,7 +1500,7 @@ static void forward(ucdir_ctx* c, const float* cond, const float* xt, const floa
                                cur->stats, 1.0 / ((double)C * c->Hc * c->Wc), c->fin_gamma, c->fin_beta);
             HIPC(hipGetLastError());
             Act dummy; dummy.B = B; dummy.H = c->Hc; dummy.W = c->Wc; dummy.C = c->fin_conv.cout;
-            run_conv(c->fin_conv, c->fin_act, nullptr, dummy, COLS_S1, 0, nullptr, false, st, eps, c->H, c->W);
+            run_conv(c->fin_conv, COLS_S1, {c->fin_act, nullptr, dummy, 0, nullptr, false, nullptr, nullptr, eps, c->H, c->W}, st);
         }
     }
 }
@@ -2046,7 +1964,7 @@ int32_t ucdir_profile_read(int32_t cap, int32_t* keys, int32_t* launches, double
     API_BEGIN
     HIPC(hipStreamSynchronize((hipStream_t)stream));
     std::map<int, int> idx; int n = 0;
-    static const bool detail = getenv("UCDIR_PROF_DETAIL") != nullptr;
+    const bool detail = env().prof_detail;
     struct Det { int n = 0; double ms = 0, flops = 0; };
     std::map<std::array<int, 5>, Det> det;
     for (auto& e : g_prof.entries) {
@@ -2102,6 +2020,20 @@ static Act act_from_nchw(DevPool& pool, const float* x, int B, int C, int H, int
     return a;
 }
 
+// end of a single-operator call: waits for the stream; the output's GroupNorm statistics (sum, sum of squares per sample) if asked for
+static void read_stats(const Act& out, int B, double* stats_out_host, hipStream_t st) {
+    std::vector<stat_t> sfx;
+    if (stats_out_host) { sfx.resize((size_t)2 * UCDIR_STAT_SLOTS * B); HIPC(hipMemcpyAsync(sfx.data(), out.stats, sizeof(stat_t) * sfx.size(), hipMemcpyDeviceToHost, st)); }
+    HIPC(hipStreamSynchronize(st));
+    if (stats_out_host)
+        for (int bb = 0; bb < B; ++bb)
+            for (int q = 0; q < 2; ++q) {                   // fixed-point slots -> (sum, sum of squares)
+                stat_t acc = 0;
+                for (int k = 0; k < UCDIR_STAT_SLOTS; ++k) acc += sfx[((size_t)bb * UCDIR_STAT_SLOTS + k) * 2 + q];
+                stats_out_host[bb * 2 + q] = (double)acc / UCDIR_STAT_SCALE;
+            }
+}
+
 int32_t ucdir_op_conv(const float* x0, int32_t c0, const float* x1, int32_t c1, int32_t B, int32_t H, int32_t W,
                       const float* w_host, const float* bias_host, const float* gamma_host, const float* beta_host,
                       int32_t cout, int32_t ksize, int32_t mode, int32_t silu, const float* residual, float* y,
@@ -2118,19 +2050,10 @@ int32_t ucdir_op_conv(const float* x0, int32_t c0, const float* x1, int32_t c1, 
     Act res; if (residual) res = act_from_nchw(pool, residual, B, cout, Ho, Wo, st, false);
     ConvW w = upload_conv(pool, w_host, bias_host, gamma_host, beta_host, cout, c0 + (x1 ? c1 : 0), ksize);
     if (mode == COLS_UP && ksize == 3) upload_upconv(pool, w, w_host, bias_host);
-    run_conv(w, a0, x1 ? &a1 : nullptr, out, mode, silu, residual ? &res : nullptr, true, st);
+    run_conv(w, mode, {a0, x1 ? &a1 : nullptr, out, silu, residual ? &res : nullptr, true}, st);
     hipLaunchKernelGGL(act_to_nchw_kernel, dim3(2048), dim3(256), 0, st, out.p, y, B, cout, Ho, Wo);
     HIPC(hipGetLastError());
-    std::vector<stat_t> sfx;
-    if (stats_out_host) { sfx.resize((size_t)2 * UCDIR_STAT_SLOTS * B); HIPC(hipMemcpyAsync(sfx.data(), out.stats, sizeof(stat_t) * sfx.size(), hipMemcpyDeviceToHost, st)); }
-    HIPC(hipStreamSynchronize(st));
-    if (stats_out_host)
-        for (int bb = 0; bb < B; ++bb)
-            for (int q = 0; q < 2; ++q) {                   // fixed-point slots -> (sum, sum of squares)
-                stat_t acc = 0;
-                for (int k = 0; k < UCDIR_STAT_SLOTS; ++k) acc += sfx[((size_t)bb * UCDIR_STAT_SLOTS + k) * 2 + q];
-                stats_out_host[bb * 2 + q] = (double)acc / UCDIR_STAT_SCALE;
-            }
+    read_stats(out, B, stats_out_host, st);
     API_END
 }
 
@@ -2157,21 +2080,12 @@ int32_t ucdir_op_conv_res(const float* x0, int32_t c0, const float* x1, int32_t 
         w.A10 = pool.upload(a10); w.bias_res = wr.bias;
         if (cin == 128 && cout == 64) w.Aws128 = pool.upload(pack_conv_ws128(a10));
     }
-    const bool did = run_conv(w, a0, x1 ? &a1 : nullptr, out, COLS_S1, silu, nullptr, true, st, nullptr, 0, 0, &rout, &wr);
-    if (!did) run_conv(wr, a0, x1 ? &a1 : nullptr, rout, COLS_S1, 0, nullptr, false, st);
+    const bool did = run_conv(w, COLS_S1, {a0, x1 ? &a1 : nullptr, out, silu, nullptr, true, &rout, &wr}, st);
+    if (!did) run_conv(wr, COLS_S1, {a0, x1 ? &a1 : nullptr, rout, 0, nullptr, false}, st);
     hipLaunchKernelGGL(act_to_nchw_kernel, dim3(2048), dim3(256), 0, st, out.p, y, B, cout, H, W);
     hipLaunchKernelGGL(act_to_nchw_kernel, dim3(2048), dim3(256), 0, st, rout.p, yres, B, cout, H, W);
     HIPC(hipGetLastError());
-    std::vector<stat_t> sfx;
-    if (stats_out_host) { sfx.resize((size_t)2 * UCDIR_STAT_SLOTS * B); HIPC(hipMemcpyAsync(sfx.data(), out.stats, sizeof(stat_t) * sfx.size(), hipMemcpyDeviceToHost, st)); }
-    HIPC(hipStreamSynchronize(st));
-    if (stats_out_host)
-        for (int bb = 0; bb < B; ++bb)
-            for (int q = 0; q < 2; ++q) {
-                stat_t acc = 0;
-                for (int k = 0; k < UCDIR_STAT_SLOTS; ++k) acc += sfx[((size_t)bb * UCDIR_STAT_SLOTS + k) * 2 + q];
-                stats_out_host[bb * 2 + q] = (double)acc / UCDIR_STAT_SCALE;
-            }
+    read_stats(out, B, stats_out_host, st);
     API_END
 }
 
@@ -2194,16 +2108,7 @@ int32_t ucdir_op_akgm(const float* h, const float* att, const float* res, int32_
     run_akgm(w, ah, G, attw, ar, out, tcbuf, st);
     hipLaunchKernelGGL(act_to_nchw_kernel, dim3(2048), dim3(256), 0, st, out.p, y, B, C, H, W);
     HIPC(hipGetLastError());
-    std::vector<stat_t> sfx;
-    if (stats_out_host) { sfx.resize((size_t)2 * UCDIR_STAT_SLOTS * B); HIPC(hipMemcpyAsync(sfx.data(), out.stats, sizeof(stat_t) * sfx.size(), hipMemcpyDeviceToHost, st)); }
-    HIPC(hipStreamSynchronize(st));
-    if (stats_out_host)
-        for (int bb = 0; bb < B; ++bb)
-            for (int q = 0; q < 2; ++q) {                   // fixed-point slots -> (sum, sum of squares)
-                stat_t acc = 0;
-                for (int k = 0; k < UCDIR_STAT_SLOTS; ++k) acc += sfx[((size_t)bb * UCDIR_STAT_SLOTS + k) * 2 + q];
-                stats_out_host[bb * 2 + q] = (double)acc / UCDIR_STAT_SCALE;
-            }
+    read_stats(out, B, stats_out_host, st);
     API_END
 }
 
@@ -2356,14 +2261,14 @@ static void predictor_forward(ucdir_predictor* c, const float* x, float* y, hipS
                            c->in_w, A("a1").p, (stat_t*)nullptr, tx * ty, 1, B);
         HIPC(hipGetLastError());
     }
-    run_conv(CV("conv1_2"), A("a1"), nullptr, A("c1"), COLS_S1, 2, nullptr, false, st);
+    run_conv(CV("conv1_2"), COLS_S1, {A("a1"), nullptr, A("c1"), 2, nullptr, false}, st);
     for (int l = 1; l <= 4; ++l) {
         const std::string L = std::to_string(l), N = std::to_string(l + 1);
         Act& src = A("c" + L); Act& dst = A("p" + L);
         hipLaunchKernelGGL(maxpool2_kernel, dim3(2048), dim3(256), 0, st, src.p, dst.p, B, src.H, src.W, src.C);
         HIPC(hipGetLastError());
-        run_conv(CV("conv" + N + "_1"), dst, nullptr, A("a" + N), COLS_S1, 2, nullptr, false, st);
-        run_conv(CV("conv" + N + "_2"), A("a" + N), nullptr, A("c" + N), COLS_S1, 2, nullptr, false, st);
+        run_conv(CV("conv" + N + "_1"), COLS_S1, {dst, nullptr, A("a" + N), 2, nullptr, false}, st);
+        run_conv(CV("conv" + N + "_2"), COLS_S1, {A("a" + N), nullptr, A("c" + N), 2, nullptr, false}, st);
     }
     const Act* cur = &A("c5");
     for (int l = 6; l <= 9; ++l) {
@@ -2383,8 +2288,8 @@ static void predictor_forward(ucdir_predictor* c, const float* x, float* y, hipS
             launch_cgemm(p, w.TM, EPI_STD, st);
         }
         const Act& skip = A("c" + std::to_string(10 - l));
-        run_conv(CV("conv" + L + "_1"), up, &skip, A("a" + L), COLS_S1, 2, nullptr, false, st);
-        run_conv(CV("conv" + L + "_2"), A("a" + L), nullptr, A("c" + L), COLS_S1, 2, nullptr, false, st);
+        run_conv(CV("conv" + L + "_1"), COLS_S1, {up, &skip, A("a" + L), 2, nullptr, false}, st);
+        run_conv(CV("conv" + L + "_2"), COLS_S1, {A("a" + L), nullptr, A("c" + L), 2, nullptr, false}, st);
         cur = &A("c" + L);
     }
     {   // conv10_1 (1x1, 32 -> 3), fp32 NCHW cropped to H x W
