@@ -180,6 +180,24 @@ int64_t ucdir_jpeg_roundtrip_workspace_bytes(int32_t B, int32_t H, int32_t W);
 int32_t ucdir_jpeg_roundtrip(const uint8_t* in, uint8_t* out, int32_t B, int32_t H, int32_t W,
                              int32_t quality, int32_t bgr, void* workspace, void* stream);
 
+/* Pillow-exact image resampling of the 4x super-resolution val task (additive in ABI 5; the reference degrades every HR crop with
+ * PIL.Image.resize(..., BICUBIC), data/LRHR_dataset.py:385-443): byte for byte what PIL.Image.resize makes of an 8-bit RGB image.
+ * filter: 0 box, 1 bilinear, 2 bicubic, 3 Lanczos.
+ * ucdir_resample_coeffs (host only, no device needed): Pillow's fixed-point table of one axis.  *ksize = taps per output sample;
+ * kk: out_size * ksize coefficients (2^22 = 1.0, zero past each row's count), bounds: out_size (first input index, count) pairs.
+ * kk and bounds may both be null to query ksize.
+ * ucdir_resample: in (B, Hin, Win, 3) -> out (B, Hout, Wout, 3), uint8, HWC, contiguous, in != out.  The horizontal pass runs
+ * first and rounds into a uint8 intermediate; an axis whose size does not change is skipped; equal sizes copy.  A per-axis ratio
+ * whose ksize exceeds 129 is refused (16:1 fits for every filter).  workspace: device buffer of
+ * ucdir_resample_workspace_bytes(B, Hin, Win, Hout, Wout) bytes (-1 on a bad shape; sized for any filter), 16-byte aligned; it
+ * receives the tables (uploaded on `stream`) and the intermediate.  No allocation; the table upload from host memory may wait for
+ * earlier work on `stream`. */
+int32_t ucdir_resample_coeffs(int32_t in_size, int32_t out_size, int32_t filter,
+                              int32_t* kk, int32_t* bounds, int32_t* ksize);
+int64_t ucdir_resample_workspace_bytes(int32_t B, int32_t Hin, int32_t Win, int32_t Hout, int32_t Wout);
+int32_t ucdir_resample(const uint8_t* in, uint8_t* out, int32_t B, int32_t Hin, int32_t Win,
+                       int32_t Hout, int32_t Wout, int32_t filter, void* workspace, void* stream);
+
 /* ---- introspection (tests / profiling) ---------------------------------------------------
  * Copy the activation a layer produced in the last forward into dst as (B,C,Hc,Wc) fp32 NCHW
  * (Hc, Wc = compute size).  layer = state_dict prefix ("downs.0", "ups.7", "mid.0", ...),

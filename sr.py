@@ -30,9 +30,9 @@ sys.path.insert(0, ROOT)
 from ucdir_amd import config as Config  # noqa: E402
 from ucdir_amd import metrics as Metrics  # noqa: E402
 from ucdir_amd import model as Model  # noqa: E402
-from ucdir_amd.data import ImagenetJPGDataset, PairDataset  # noqa: E402
+from ucdir_amd.data import ImagenetJPGDataset, ImagenetSRDataset, PairDataset  # noqa: E402
 
-VAL_DATASETS = {"PairDataset": PairDataset, "ImagenetJPGDataset": ImagenetJPGDataset}
+VAL_DATASETS = {"PairDataset": PairDataset, "ImagenetJPGDataset": ImagenetJPGDataset, "ImagenetSRDataset": ImagenetSRDataset}
 
 
 def make_val_dataset(val_opt):

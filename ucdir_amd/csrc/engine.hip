@@ -32,6 +32,7 @@
 #include "fewstep.hip.h"
 #include "image_metrics.hip.h"
 #include "jpeg_roundtrip.hip.h"
+#include "resample.hip.h"
 #include "pack.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -1870,6 +1871,100 @@ int32_t ucdir_jpeg_roundtrip(const uint8_t* in, uint8_t* out, int32_t B, int32_t
     hipLaunchKernelGGL(jpeg_upsample_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        (const unsigned char*)workspace, out, B, H, W, bgr ? 1 : 0);
     HIPC(hipGetLastError());
+    API_END
+}
+
+// Pillow-exact resampling of the super-resolution val task (csrc/resample.hip.h).  Table layout in the workspace: per changing
+// axis out_size * ksize coefficients then out_size (min, count) pairs, horizontal axis first; 16-byte rounded; then the
+// intermediate image.
+static const char* resample_check(int32_t B, int32_t Hin, int32_t Win, int32_t Hout, int32_t Wout, int32_t filter) {
+    if (B < 1 || Hin < 1 || Win < 1 || Hout < 1 || Wout < 1) return "sizes must be at least 1";
+    if (filter < 0 || filter > 3) return "unknown filter (0 box, 1 bilinear, 2 bicubic, 3 Lanczos)";
+    if (Hin > 65536 || Win > 65536 || Hout > 65536 || Wout > 65536) return "sides above 65536 are not supported";
+    if ((int64_t)B * std::max(Hin, Hout) >= (1LL << 31)) return "more than 2^31 - 1 rows";
+    if ((Win != Wout && resample::ksize_of(Win, Wout, filter) > RESAMPLE_MAX_KSIZE) ||
+        (Hin != Hout && resample::ksize_of(Hin, Hout, filter) > RESAMPLE_MAX_KSIZE))
+        return "ratio too large: the filter would span more than 129 taps (ksize cap)";
+    return nullptr;
+}
+
+static int64_t resample_table_ints(int32_t in_size, int32_t out_size, int32_t filter_ksize) {
+    return in_size == out_size ? 0 : (int64_t)out_size * (filter_ksize + 2);
+}
+
+int32_t ucdir_resample_coeffs(int32_t in_size, int32_t out_size, int32_t filter, int32_t* kk, int32_t* bounds, int32_t* ksize) {
+    API_BEGIN
+    const std::string w("ucdir_resample_coeffs");
+    require(in_size >= 1 && out_size >= 1, w + ": sizes must be at least 1");
+    require(filter >= 0 && filter <= 3, w + ": unknown filter (0 box, 1 bilinear, 2 bicubic, 3 Lanczos)");
+    require(ksize, w + ": null argument");
+    require((kk == nullptr) == (bounds == nullptr), w + ": kk and bounds must both be given or both be null");
+    const int ks = resample::ksize_of(in_size, out_size, filter);
+    require(ks <= (1 << 20), w + ": ratio too large");
+    *ksize = ks;
+    if (kk) resample::coeffs(in_size, out_size, filter, ks, kk, bounds);
+    API_END
+}
+
+int64_t ucdir_resample_workspace_bytes(int32_t B, int32_t Hin, int32_t Win, int32_t Hout, int32_t Wout) {
+    if (resample_check(B, Hin, Win, Hout, Wout, 0)) return -1;
+    // sized for any filter a call accepts: the widest one, Lanczos, up to the tap cap
+    const int64_t ints = resample_table_ints(Win, Wout, std::min(resample::ksize_of(Win, Wout, 3), RESAMPLE_MAX_KSIZE)) +
+                         resample_table_ints(Hin, Hout, std::min(resample::ksize_of(Hin, Hout, 3), RESAMPLE_MAX_KSIZE));
+    const int64_t tmp = (Win != Wout && Hin != Hout) ? (int64_t)B * Hin * Wout * 3 : 0;
+    return std::max<int64_t>((ints * 4 + 15) / 16 * 16 + tmp, 16);
+}
+
+int32_t ucdir_resample(const uint8_t* in, uint8_t* out, int32_t B, int32_t Hin, int32_t Win, int32_t Hout, int32_t Wout,
+                       int32_t filter, void* workspace, void* stream) {
+    API_BEGIN
+    const std::string w("ucdir_resample");
+    require(in && out && workspace, w + ": null argument");
+    const char* bad = resample_check(B, Hin, Win, Hout, Wout, filter);
+    require(!bad, w + ": " + (bad ? bad : ""));
+    require(in != out, w + ": in and out must differ");
+    require(((uintptr_t)workspace & 15) == 0, w + ": workspace must be 16-byte aligned");
+    hipPointerAttribute_t pa;
+    HIPC(hipPointerGetAttributes(&pa, in));
+    require(pa.type == hipMemoryTypeDevice, w + ": in is not a device pointer");
+    const void* others[2] = {out, workspace};
+    const char* names[2] = {"out", "workspace"};
+    for (int i = 0; i < 2; ++i) {
+        hipPointerAttribute_t po;
+        HIPC(hipPointerGetAttributes(&po, others[i]));
+        require(po.type == hipMemoryTypeDevice && po.device == pa.device, w + ": " + names[i] + " must live on the device of in");
+    }
+    const bool horiz = Win != Wout, vert = Hin != Hout;
+    const int ksh = horiz ? resample::ksize_of(Win, Wout, filter) : 0, ksv = vert ? resample::ksize_of(Hin, Hout, filter) : 0;
+    const int64_t ints_h = resample_table_ints(Win, Wout, ksh), ints_v = resample_table_ints(Hin, Hout, ksv);
+    DevGuard dg(pa.device);
+    hipStream_t st = (hipStream_t)stream;
+    if (!horiz && !vert) {                                      // Pillow's resize to the same size: a copy
+        HIPC(hipMemcpyAsync(out, in, (size_t)B * Hin * Win * 3, hipMemcpyDeviceToDevice, st));
+        return 0;
+    }
+    // The tables go up from pageable host memory: such a copy has left the host buffer when hipMemcpyAsync returns.
+    std::vector<int32_t> tab((size_t)(ints_h + ints_v));
+    int32_t* const d_tab = (int32_t*)workspace;
+    if (horiz) resample::coeffs(Win, Wout, filter, ksh, tab.data(), tab.data() + (size_t)Wout * ksh);
+    if (vert) resample::coeffs(Hin, Hout, filter, ksv, tab.data() + ints_h, tab.data() + ints_h + (size_t)Hout * ksv);
+    HIPC(hipMemcpyAsync(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, st));
+    unsigned char* const tmp = (unsigned char*)workspace + ((ints_h + ints_v) * 4 + 15) / 16 * 16;
+    const unsigned char* vsrc = in;
+    if (horiz) {
+        const long long rows = (long long)B * Hin;
+        const dim3 grid((unsigned)((rows + RESAMPLE_RY - 1) / RESAMPLE_RY), (unsigned)((Wout + RESAMPLE_TX - 1) / RESAMPLE_TX));
+        hipLaunchKernelGGL(resample_h_kernel, grid, dim3(RESAMPLE_TX * 3), (size_t)RESAMPLE_TX * (ksh + 2) * 4, st, in,
+                           vert ? tmp : out, (const int*)d_tab, (const int*)d_tab + (size_t)Wout * ksh, rows, Win, Wout, ksh);
+        HIPC(hipGetLastError());
+        vsrc = tmp;
+    }
+    if (vert) {
+        const int N = Wout * 3;
+        hipLaunchKernelGGL(resample_v_kernel, dim3((unsigned)(B * Hout), (unsigned)((N + 255) / 256)), dim3(256), 0, st, vsrc, out,
+                           (const int*)d_tab + ints_h, (const int*)d_tab + ints_h + (size_t)Hout * ksv, Hin, Hout, N, ksv);
+        HIPC(hipGetLastError());
+    }
     API_END
 }
 

@@ -1,6 +1,7 @@
 """Paired-image loader for ``-p val`` (reference: data/LRHR_dataset.py:230-297 PairDataset, val split, datatype img):
 sorted file lists of dataroot.lq / dataroot.gt, RGB, scaled to [-1, 1] (data/util.py:76-83), dict with 'HR', 'SR', 'LR',
-'Index'; and the JPEG-restoration loader ImagenetJPGDataset (reference: data/LRHR_dataset.py:446-516)."""
+'Index'; the JPEG-restoration loader ImagenetJPGDataset (reference: data/LRHR_dataset.py:446-516); and the 4x super-resolution
+loader ImagenetSRDataset (reference: data/LRHR_dataset.py:385-443)."""
 import os
 
 import numpy as np
@@ -102,5 +103,65 @@ class ImagenetJPGDataset:
         from .metrics import jpeg_roundtrip_device
         hr_u8 = torch.from_numpy(self.load_u8(i)).to(torch.device("cuda", torch.cuda.current_device()))
         sr_u8 = jpeg_roundtrip_device(hr_u8, self.quality(i), bgr=True)
+        sr = _u8_to_unit(sr_u8)
+        return {"HR": _u8_to_unit(hr_u8), "SR": sr, "LR": sr, "Index": i}
+
+
+def sr_geometry(w, h, size=256):
+    """Host-only geometry of the SR loader for a (w, h) image -> (pre, (left, top, s)).  ``pre`` is None or the (w, h) the image is
+    resized to first: when its shorter side is below ``size`` that side becomes ``size`` and the longer int(size * long / short)
+    (torchvision's resize to an int).  Then the centered square crop of side s = min(w, h), placed with Python's round as
+    torchvision's center_crop places it (a .5 goes to the even neighbour)."""
+    pre = None
+    if min(w, h) < size:
+        pre = (size, int(size * h / w)) if w <= h else (int(size * w / h), size)
+        w, h = pre
+    s = min(w, h)
+    return pre, (int(round((w - s) / 2.0)), int(round((h - s) / 2.0)), s)
+
+
+class ImagenetSRDataset:
+    """4x super-resolution val loader (reference: data/LRHR_dataset.py:385-443, ImagenetSRDataset): file names from the first field
+    of each line of dataroot.txt under dataroot.root.  The image is decoded on the host and uploaded once; HR = the centered square
+    crop resized to 256^2, LR64 = HR resized to 64^2, SR = LR64 resized back to 256^2, all bicubic and all computed on the current
+    GPU with Pillow's arithmetic (csrc/resample.hip.h), so HR and SR equal the reference's PIL images byte for byte.  The 64^2
+    image of the last item stays reachable as ``last_lr64``."""
+    sizes = (64, 256)
+
+    def __init__(self, data_args, phase="val"):
+        root = data_args["dataroot"]
+        self.root = root["root"]
+        with open(root["txt"]) as f:
+            names = [ln.split()[0] for ln in f if ln.strip()]
+        n = data_args.get("data_len", -1)
+        if n and n > 0:
+            names = names[:n]
+        self.hr_path = [os.path.join(self.root, s) for s in names]
+        self.sr_path = self.hr_path                  # sr.py names its outputs after sr_path
+        self.last_lr64 = None
+
+    def __len__(self):
+        return len(self.hr_path)
+
+    def load_u8(self, i):
+        """Host half: decode to RGB -> (H, W, 3) uint8, contiguous; every resize and the crop happen on the device."""
+        from PIL import Image
+        return np.array(Image.open(self.hr_path[i]).convert("RGB"), dtype=np.uint8)
+
+    def degrade_u8(self, img_u8):
+        """Device half on an uploaded (H, W, 3) uint8 image -> (HR 256^2, LR 64^2, SR 256^2), uint8."""
+        from .metrics import resample_device
+        lo, hi = self.sizes
+        pre, (left, top, s) = sr_geometry(img_u8.shape[1], img_u8.shape[0], hi)
+        if pre is not None:
+            img_u8 = resample_device(img_u8, (pre[1], pre[0]), "bicubic")
+        crop = img_u8[top:top + s, left:left + s].contiguous()
+        hr = resample_device(crop, (hi, hi), "bicubic")
+        lr64 = resample_device(hr, (lo, lo), "bicubic")
+        return hr, lr64, resample_device(lr64, (hi, hi), "bicubic")
+
+    def __getitem__(self, i):
+        img = torch.from_numpy(self.load_u8(i)).to(torch.device("cuda", torch.cuda.current_device()))
+        hr_u8, self.last_lr64, sr_u8 = self.degrade_u8(img)
         sr = _u8_to_unit(sr_u8)
         return {"HR": _u8_to_unit(hr_u8), "SR": sr, "LR": sr, "Index": i}

@@ -136,3 +136,44 @@ def jpeg_roundtrip_device(x_u8, quality, bgr=True):
     out = torch.empty_like(x_u8)
     lib.check(L.ucdir_jpeg_roundtrip(_ptr(x), _ptr(out), B, H, W, int(quality), 1 if bgr else 0, _ptr(ws), _stream_ptr(x.device)))
     return out
+
+
+RESAMPLE_FILTERS = {"box": 0, "bilinear": 1, "bicubic": 2, "lanczos": 3}
+
+
+def resample_device(x_u8, size, filter="bicubic"):
+    """PIL.Image.resize of uint8 RGB images on the GPU (csrc/resample.hip.h): byte for byte what Pillow's 8-bit resampling makes of
+    them.  ``x_u8``: (B, H, W, 3) or (H, W, 3) contiguous uint8 CUDA tensor; ``size``: (Hout, Wout); ``filter``: one of
+    RESAMPLE_FILTERS -> a new tensor of the same rank on the same device, computed on the current stream.  Equal sizes copy, as
+    Pillow does."""
+    import torch
+    from . import lib
+    from .ucdir import _ptr, _stream_ptr
+    if not torch.is_tensor(x_u8) or not x_u8.is_cuda:
+        raise ValueError("resample_device takes a uint8 tensor on the GPU")
+    if x_u8.dtype != torch.uint8:
+        raise ValueError(f"resample_device takes uint8 images, got {x_u8.dtype}")
+    if x_u8.dim() not in (3, 4) or x_u8.shape[-1] != 3 or x_u8.numel() == 0:
+        raise ValueError(f"resample_device takes (B, H, W, 3) or (H, W, 3) images, got {tuple(x_u8.shape)}")
+    if not x_u8.is_contiguous():
+        raise ValueError("resample_device takes a contiguous tensor")
+    try:
+        Hout, Wout = size
+        ok = all(not isinstance(v, bool) and int(v) == v and v >= 1 for v in (Hout, Wout))
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"resample_device: size must be (Hout, Wout) with positive integers, got {size!r}")
+    if filter not in RESAMPLE_FILTERS:
+        raise ValueError(f"resample_device: filter must be one of {', '.join(RESAMPLE_FILTERS)}, got {filter!r}")
+    Hout, Wout = int(Hout), int(Wout)
+    x = x_u8 if x_u8.dim() == 4 else x_u8.unsqueeze(0)
+    B, H, W, _ = x.shape
+    L = lib.load()
+    nbytes = L.ucdir_resample_workspace_bytes(B, H, W, Hout, Wout)
+    if nbytes < 0:
+        raise ValueError(f"resample_device: {H} x {W} -> {Hout} x {Wout} is outside what ucdir_resample supports (include/ucdir_hip.h)")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    out = torch.empty((B, Hout, Wout, 3), dtype=torch.uint8, device=x.device)
+    lib.check(L.ucdir_resample(_ptr(x), _ptr(out), B, H, W, Hout, Wout, RESAMPLE_FILTERS[filter], _ptr(ws), _stream_ptr(x.device)))
+    return out if x_u8.dim() == 4 else out[0]
