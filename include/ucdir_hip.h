@@ -198,6 +198,26 @@ int64_t ucdir_resample_workspace_bytes(int32_t B, int32_t Hin, int32_t Win, int3
 int32_t ucdir_resample(const uint8_t* in, uint8_t* out, int32_t B, int32_t Hin, int32_t Win,
                        int32_t Hout, int32_t Wout, int32_t filter, void* workspace, void* stream);
 
+/* NIQE features of the val loop (additive in ABI 5; the reference's metric/niqe.py calculate_niqe(img, 0, 'HWC', 'y') up to its last,
+ * 36 x 36 step, which stays on the host).  x: fp32 (B, C, H, W) in [-1, 1], C = 3 (RGB) or 1, strides as for ucdir_image_metrics;
+ * every pixel is quantised like tensor2img_u8_device first.  The image is cropped to its top-left nh x nw = (H / 96) x (W / 96)
+ * whole blocks.  Per image and block k = iw * nh + ih, feats[(n * nblk + k) * 36 ..] receives 18 float64 features of scale 1 then
+ * 18 of the half-size scale: [alpha, (bl + br) / 2], then [alpha, mean, bl, br] for the shifts (0,1), (1,0), (1,1), (1,-1); a flat
+ * block yields alpha = 0.2 and NaNs, as the reference.  The MSCN planes are float32 and bit-equal to the reference's arithmetic
+ * with scipy's filter; the block statistics are float64.
+ *   window49: 49 float64 of the 7x7 Gaussian window, row-major, in HOST memory (read before the call returns);
+ *   tables:   4 x 9801 float64 ON THE DEVICE: gamma(1/a), gamma(2/a), gamma(3/a), g2^2 / (g1 g3) on a = 0.2 + 0.001 i;
+ *   mscn_or_null: when given, a device buffer of B * 5/4 * (96 nh) * (96 nw) floats that receives, per image, the scale-1 plane then
+ *             the scale-2 plane (otherwise they live in the workspace);
+ *   workspace: device buffer of ucdir_niqe_workspace_bytes(B, C, H, W) bytes, 8-byte aligned; negative when H / 96 * (W / 96) < 1
+ *             or C is not 1 or 3.
+ * No atomics, no allocation, no synchronisation: two calls return identical bits. */
+int64_t ucdir_niqe_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W);
+int32_t ucdir_niqe_features(const float* x, int64_t x_sn, int64_t x_sc, int64_t x_sh,
+                            int32_t B, int32_t C, int32_t H, int32_t W,
+                            const double* window49, const double* tables, double* feats,
+                            float* mscn_or_null, void* workspace, void* stream);
+
 /* ---- introspection (tests / profiling) ---------------------------------------------------
  * Copy the activation a layer produced in the last forward into dst as (B,C,Hc,Wc) fp32 NCHW
  * (Hc, Wc = compute size).  layer = state_dict prefix ("downs.0", "ups.7", "mid.0", ...),

@@ -3,7 +3,7 @@
 
 Counterpart of the reference's ``sr.py`` val branch (sr.py:320-400, 505-586): same flags, same YAML
 schema, same per-image outputs ``{results}/{fname}_{name}_{sr,hr,lr,inf}.jpg`` and the
-``# Validation # PSNR/SSIM`` log lines.  One process per GPU; with N ranks
+``# Validation # PSNR/SSIM`` log lines; ``--niqe`` adds the no-reference score of the reference's ``eval1.py``.  One process per GPU; with N ranks
 (``python -m torch.distributed.run --nproc-per-node N sr.py ...``):
   * images small enough for one denoiser call are strided over ranks like the reference's EnlargedSampler
     (data/data_sampler.py:44-45), no data-path collective;
@@ -95,6 +95,10 @@ def make_parser():
     parser.add_argument("--ddim-eta", type=float, default=None, help="ddim noise scale (0: deterministic, 1: the reference's setting)")
     parser.add_argument("--metrics-device", choices=["cpu", "gpu"], default="cpu",
                         help="score PSNR / SSIM on the host (numpy / scipy) or on the GPU (HIP kernel, the same uint8 images)")
+    parser.add_argument("--niqe", action="store_true",
+                        help="also score the restored images with NIQE, the no-reference score of the reference's eval1.py")
+    parser.add_argument("--niqe-params", type=str, default="./metric/niqe_pris_params.npz",
+                        help="pristine-model statistics of NIQE (the reference's metric/niqe_pris_params.npz)")
     return parser
 
 
@@ -120,10 +124,12 @@ def main(argv=None):
     fh = logging.FileHandler(os.path.join(opt["path"]["log"], "val.log"))
     logging.getLogger("val").addHandler(fh)
 
+    niqe_params = Metrics.load_niqe_params(args.niqe_params) if args.niqe else None      # a missing file stops the run here
     val_set = make_val_dataset(opt["datasets"]["val"])
     if args.synthetic_weights:
         opt["path"]["resume_state"] = None
     diffusion = Model.create_model(opt)
+    diffusion.niqe_params = niqe_params
     if args.synthetic_weights:
         from ucdir_amd.weights import synth_state_dict
         sd = synth_state_dict(diffusion.netG.denoise_fn.cfg, 0)
@@ -133,7 +139,7 @@ def main(argv=None):
     logger.info("Begin Model Evaluation. len %d" % len(val_set))
     result_path = opt["path"]["results"]
     os.makedirs(result_path, exist_ok=True)
-    tot_psnr = tot_ssim = 0.0
+    tot_psnr = tot_ssim = tot_niqe = 0.0
     n = 0
     idxs = list(range(len(val_set)))
     if args.max_images > 0:
@@ -150,7 +156,7 @@ def main(argv=None):
     def restore(group):
         """One DDPM.test call for a group of images of identical (H, W): a batch is B independent restorations (model/diffusion.py:185-211
         is written for a batch; the reference's val loader feeds it batch_size 1, data/__init__.py:47)."""
-        nonlocal tot_psnr, tot_ssim, n, t_restore, n_restored
+        nonlocal tot_psnr, tot_ssim, tot_niqe, n, t_restore, n_restored
         items = [g[1] for g in group]
         data = {k: torch.stack([it[k] for it in items]) for k in ("HR", "SR", "LR") if k in items[0]}
         data["Index"] = [g[0] for g in group]                    # DDPM.test derives every image's noise stream from its index
@@ -169,6 +175,7 @@ def main(argv=None):
             return                                                # sharded image: every rank holds the same result; rank 0 reports it
         name = opt["name"]
         dev_scores = diffusion.current_metrics() if args.metrics_device == "gpu" else None
+        dev_niqe = diffusion.current_niqe() if args.niqe and args.metrics_device == "gpu" else None
         for j, (i, _, _) in enumerate(group):
             fname = os.path.splitext(os.path.basename(val_set.sr_path[i]))[0]
             vis = diffusion.visuals_u8(j)
@@ -183,6 +190,8 @@ def main(argv=None):
             else:
                 tot_psnr += Metrics.calculate_psnr(sr_img, hr_img)
                 tot_ssim += Metrics.calculate_ssim(sr_img, hr_img)
+            if args.niqe:                                         # the uint8 SR image itself, not the JPEG read back
+                tot_niqe += dev_niqe[j] if dev_niqe is not None else Metrics.calculate_niqe(sr_img, niqe_params)
             n += 1
             logger.info("val index %d" % i)
 
@@ -211,13 +220,18 @@ def main(argv=None):
         logger.info("restored %d images in %.2f s on this rank (%.2f img/s, batches of up to %d)" % (n_restored, t_restore, n_restored / t_restore, args.batch))
     main.last_throughput = (n_restored, t_restore)
     main.last_groups = group_times
-    acc = torch.tensor([tot_psnr, tot_ssim, float(n)], dtype=torch.float64, device="cuda")
+    acc = torch.tensor([tot_psnr, tot_ssim, float(n), tot_niqe], dtype=torch.float64, device="cuda")
     if world > 1:
         dist.all_reduce(acc)
     avg_psnr, avg_ssim = (acc[0] / acc[2]).item(), (acc[1] / acc[2]).item()
     logger.info("# Validation # PSNR: {:.4e}".format(avg_psnr))
     logger.info("# Validation # SSIM: {:.4e}".format(avg_ssim))
-    logging.getLogger("val").info("psnr: {:.4e}, ssim: {:.4e}".format(avg_psnr, avg_ssim))
+    main.last_niqe = (acc[3] / acc[2]).item() if args.niqe else None
+    if args.niqe:
+        logger.info("# Validation # NIQE: {:.4e}".format(main.last_niqe))
+        logging.getLogger("val").info("psnr: {:.4e}, ssim: {:.4e}, niqe: {:.4e}".format(avg_psnr, avg_ssim, main.last_niqe))
+    else:
+        logging.getLogger("val").info("psnr: {:.4e}, ssim: {:.4e}".format(avg_psnr, avg_ssim))
     if world > 1:
         dist.destroy_process_group()
     return avg_psnr, avg_ssim

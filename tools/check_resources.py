@@ -47,10 +47,10 @@ def measure():
             cur = m.group(1)
             res[cur] = {}
             continue
-        m = re.search(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|VGPRs Spill|SGPRs Spill|Occupancy \[waves/SIMD\]): (\d+)", line)
+        m = re.search(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|VGPRs Spill|SGPRs Spill|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
         if m and cur:
             key = {"ScratchSize [bytes/lane]": "scratch", "VGPRs Spill": "vgpr_spill", "SGPRs Spill": "sgpr_spill",
-                   "Occupancy [waves/SIMD]": "occupancy"}.get(m.group(1), m.group(1).lower())
+                   "Occupancy [waves/SIMD]": "occupancy", "LDS Size [bytes/block]": "lds"}.get(m.group(1), m.group(1).lower())
             res[cur][key] = int(m.group(2))
     names = list(res)
     pretty = demangle(names)

@@ -33,6 +33,7 @@
 #include "image_metrics.hip.h"
 #include "jpeg_roundtrip.hip.h"
 #include "resample.hip.h"
+#include "niqe.hip.h"
 #include "pack.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -1963,6 +1964,64 @@ int32_t ucdir_resample(const uint8_t* in, uint8_t* out, int32_t B, int32_t Hin, 
         const int N = Wout * 3;
         hipLaunchKernelGGL(resample_v_kernel, dim3((unsigned)(B * Hout), (unsigned)((N + 255) / 256)), dim3(256), 0, st, vsrc, out,
                            (const int*)d_tab + ints_h, (const int*)d_tab + ints_h + (size_t)Hout * ksv, Hin, Hout, N, ksv);
+        HIPC(hipGetLastError());
+    }
+    API_END
+}
+
+// NIQE features of the val loop (csrc/niqe.hip.h).  Workspace: the MSCN planes of both scales per image (5/4 Hc Wc floats, used when
+// the caller passes no buffer of its own), then the half-size Y planes (1/4 Hc Wc floats per image); Hc x Wc = the crop to whole
+// 96 x 96 blocks.
+int64_t ucdir_niqe_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W) {
+    if (B <= 0 || H <= 0 || W <= 0 || (C != 1 && C != 3)) return -1;
+    const int64_t nblk = (int64_t)(H / NQ_BLOCK) * (W / NQ_BLOCK);
+    if (nblk < 1) return -1;
+    return (int64_t)B * nblk * NQ_BLOCK * NQ_BLOCK * 6 / 4 * (int64_t)sizeof(float);
+}
+
+int32_t ucdir_niqe_features(const float* x, int64_t x_sn, int64_t x_sc, int64_t x_sh, int32_t B, int32_t C, int32_t H, int32_t W,
+                            const double* window49, const double* tables, double* feats, float* mscn_or_null, void* workspace,
+                            void* stream) {
+    API_BEGIN
+    const std::string w("ucdir_niqe_features");
+    require(x && window49 && tables && feats && workspace, w + ": null argument");
+    require(C == 1 || C == 3, w + ": C must be 1 or 3");
+    require(B > 0 && B <= 65535, w + ": B must lie in 1..65535");
+    require(H >= NQ_BLOCK && W >= NQ_BLOCK, w + ": H and W must be at least 96");
+    const int nh = H / NQ_BLOCK, nw = W / NQ_BLOCK, Hc = nh * NQ_BLOCK, Wc = nw * NQ_BLOCK;
+    const long long nblk = (long long)nh * nw, plane = (long long)Hc * Wc;
+    require(plane / (NQ_T / 2 * NQ_T / 2) <= 0x7fffffffLL, w + ": image too large");
+    require(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)feats & 7) == 0 && ((uintptr_t)tables & 7) == 0 &&
+            ((uintptr_t)mscn_or_null & 3) == 0, w + ": workspace, tables and feats must be 8-byte aligned, mscn 4-byte");
+    hipPointerAttribute_t pa;
+    HIPC(hipPointerGetAttributes(&pa, x));
+    require(pa.type == hipMemoryTypeDevice, w + ": x is not a device pointer");
+    const void* others[4] = {tables, feats, workspace, mscn_or_null};
+    const char* names[4] = {"tables", "feats", "workspace", "mscn"};
+    for (int i = 0; i < 4; ++i) {
+        if (!others[i]) continue;
+        hipPointerAttribute_t po;
+        HIPC(hipPointerGetAttributes(&po, others[i]));
+        require(po.type == hipMemoryTypeDevice && po.device == pa.device, w + ": " + names[i] + " must live on the device of x");
+    }
+    NiqeWindow win;
+    for (int k = 0; k < 49; ++k) win.w[k] = window49[k];
+    DevGuard dg(pa.device);
+    hipStream_t st = (hipStream_t)stream;
+    float* mscn = mscn_or_null ? mscn_or_null : (float*)workspace;
+    float* y2 = (float*)workspace + (long long)B * plane * 5 / 4;
+    const long long mscn_sn = plane * 5 / 4;
+    hipLaunchKernelGGL(niqe_mscn_kernel<1>, dim3((unsigned)(plane / (NQ_T * NQ_T)), (unsigned)B), dim3(256), 0, st, x, (long long)x_sn,
+                       (long long)x_sc, (long long)x_sh, C, Hc, Wc, win, (const float*)nullptr, mscn, mscn_sn, y2);
+    HIPC(hipGetLastError());
+    hipLaunchKernelGGL(niqe_mscn_kernel<2>, dim3((unsigned)(plane / 4 / (NQ_T * NQ_T)), (unsigned)B), dim3(256), 0, st,
+                       (const float*)nullptr, 0LL, 0LL, 0LL, 1, Hc / 2, Wc / 2, win, (const float*)y2, mscn + plane, mscn_sn,
+                       (float*)nullptr);
+    HIPC(hipGetLastError());
+    for (int scale = 1; scale <= 2; ++scale) {
+        hipLaunchKernelGGL(niqe_block_kernel, dim3((unsigned)nblk, (unsigned)B), dim3(256), 0, st,
+                           (const float*)(scale == 1 ? mscn : mscn + plane), mscn_sn, Wc / scale, NQ_BLOCK / scale, nh, (int)nblk, scale,
+                           tables, feats);
         HIPC(hipGetLastError());
     }
     API_END

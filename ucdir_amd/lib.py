@@ -57,6 +57,9 @@ _SIGS = {
     "ucdir_resample_coeffs": (c_int32, [c_int32, c_int32, c_int32, c_void_p, c_void_p, POINTER(c_int32)]),
     "ucdir_resample_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32]),
     "ucdir_resample": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "ucdir_niqe_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+    "ucdir_niqe_features": (c_int32, [c_void_p, c_int64, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p]),
     "ucdir_sampler_step": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float,
                                      c_float, c_void_p]),
     "ucdir_debug_read": (c_int32, [c_void_p, c_char_p, c_char_p, c_void_p, c_int64, c_void_p]),

@@ -177,3 +177,188 @@ def resample_device(x_u8, size, filter="bicubic"):
     out = torch.empty((B, Hout, Wout, 3), dtype=torch.uint8, device=x.device)
     lib.check(L.ucdir_resample(_ptr(x), _ptr(out), B, H, W, Hout, Wout, RESAMPLE_FILTERS[filter], _ptr(ws), _stream_ptr(x.device)))
     return out if x_u8.dim() == 4 else out[0]
+
+
+# ---- NIQE, the no-reference score of the val loop (reference metric/niqe.py calculate_niqe(img, 0, 'HWC', 'y')) ------------------
+# The recipe: the image-sized part runs in the reference's float32 steps (scipy's filter returns the input's
+# dtype), everything per block and after it in float64.  niqe_features_host / calculate_niqe are the project's CPU oracle of
+# csrc/niqe.hip.h; niqe_device is the same arithmetic on the GPU up to the summation order of the block moments.
+NIQE_BLOCK = 96
+NIQE_NGRID = 9801
+NIQE_ALPHA_COLS = (0, 2, 6, 10, 14, 18, 20, 24, 28, 32)
+_NIQE_SHIFTS = ((0, 1), (1, 0), (1, 1), (1, -1))
+_niqe_tables_cache = {}
+
+
+def load_niqe_params(path):
+    """The pristine-image model of NIQE (the reference's metric/niqe_pris_params.npz): ``mu`` (36,), ``cov`` (36, 36) and the 7x7
+    Gaussian ``window``, all float64."""
+    import os
+    if not os.path.isfile(path):
+        raise FileNotFoundError(f"NIQE pristine-model file {path!r} is missing (the reference ships it as metric/niqe_pris_params.npz; "
+                                "pass its location with --niqe-params)")
+    with np.load(path) as z:
+        return {"mu": np.asarray(z["mu_pris_param"], np.float64).reshape(-1),
+                "cov": np.asarray(z["cov_pris_param"], np.float64),
+                "window": np.ascontiguousarray(z["gaussian_window"], np.float64)}
+
+
+def niqe_tables():
+    """(4, 9801) float64: gamma(1/a), gamma(2/a), gamma(3/a) and r_gam = g2^2 / (g1 g3) on a = arange(0.2, 10.001, 0.001).  Made once;
+    the kernel evaluates no gamma function."""
+    if "t" not in _niqe_tables_cache:
+        from scipy.special import gamma
+        a = np.arange(0.2, 10.001, 0.001)
+        g1, g2, g3 = gamma(1 / a), gamma(2 / a), gamma(3 / a)
+        _niqe_tables_cache["t"] = np.ascontiguousarray(np.stack([g1, g2, g3, g2 * g2 / (g1 * g3)]))
+        _niqe_tables_cache["a"] = a
+        assert a.size == NIQE_NGRID
+    return _niqe_tables_cache["t"]
+
+
+def _niqe_check_shape(C, H, W):
+    if C not in (1, 3):
+        raise ValueError(f"NIQE takes images of 1 or 3 channels, got {C}")
+    if H < NIQE_BLOCK or W < NIQE_BLOCK:
+        raise ValueError(f"NIQE needs at least {NIQE_BLOCK} pixels on each side, got {H} x {W}")
+    if (H // NIQE_BLOCK) * (W // NIQE_BLOCK) < 2:
+        raise ValueError(f"NIQE needs at least 2 blocks of {NIQE_BLOCK} x {NIQE_BLOCK} (a covariance over blocks), got {H} x {W}")
+
+
+def niqe_y(img):
+    """Step 1: the float32 Y plane in [0, 255] of a uint8 RGB (H, W, 3) or grey (H, W) / (H, W, 1) image."""
+    img = np.asarray(img)
+    if img.dtype != np.uint8:
+        raise ValueError(f"NIQE takes uint8 images, got {img.dtype}")
+    if img.ndim == 3 and img.shape[2] not in (1, 3):
+        raise ValueError(f"NIQE takes images of 1 or 3 channels, got {img.shape[2]}")
+    if img.ndim == 3 and img.shape[2] == 1:
+        img = img[..., 0]
+    if img.ndim == 2:
+        return img.astype(np.float32)
+    if img.ndim != 3:
+        raise ValueError(f"NIQE takes (H, W, 3) or (H, W) images, got shape {img.shape}")
+    x = img.astype(np.float32) / np.float32(255)
+    r, g, b = (x[..., c].astype(np.float64) for c in range(3))
+    y64 = b * 24.966 + g * 128.553 + r * 65.481 + 16.0
+    return (y64 / 255.0).astype(np.float32) * np.float32(255)
+
+
+def niqe_mscn_host(Y, window):
+    """Step 3: (Y - mu) / (sigma + 1), float32, 7x7 window with replicated borders."""
+    from scipy.ndimage import correlate
+    Y = np.ascontiguousarray(Y, np.float32)
+    mu = correlate(Y, window, mode="nearest")
+    e2 = correlate(Y * Y, window, mode="nearest")
+    sigma = np.sqrt(np.abs(e2 - mu * mu))
+    return (Y - mu) / (sigma + np.float32(1))
+
+
+def _niqe_aggd(m, tables):
+    """estimate_aggd_param of one float32 map, in float64: (grid index, alpha, beta_l, beta_r)."""
+    v = m.astype(np.float64).ravel()
+    neg, pos = v[v < 0], v[v > 0]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        left = np.sqrt(np.float64(np.sum(neg * neg)) / np.float64(neg.size))
+        right = np.sqrt(np.float64(np.sum(pos * pos)) / np.float64(pos.size))
+        g = left / right
+        rhat = (np.sum(np.abs(v)) / v.size) ** 2 / (np.sum(v * v) / v.size + 1e-10)
+        rhatnorm = (rhat * (g * g * g + 1) * (g + 1)) / ((g * g + 1) * (g * g + 1))
+        i = 0 if np.isnan(rhatnorm) else int(np.argmin((tables[3] - rhatnorm) ** 2))
+        s = np.sqrt(tables[0][i] / tables[2][i])
+        return i, _niqe_tables_cache["a"][i], left * s, right * s
+
+
+def _niqe_block_features(block, tables):
+    i, alpha, bl, br = _niqe_aggd(block, tables)
+    feat = [alpha, (bl + br) / 2]
+    for sh in _NIQE_SHIFTS:
+        i, alpha, bl, br = _niqe_aggd(block * np.roll(block, sh, axis=(0, 1)), tables)
+        feat += [alpha, (br - bl) * (tables[1][i] / tables[0][i]), bl, br]
+    return feat
+
+
+def niqe_features_host(img, params, return_mscn=False):
+    """Steps 1-5 on the host: the (nblk, 36) float64 feature matrix of a uint8 RGB / grey image (NaN where a block is flat);
+    with ``return_mscn`` also the two float32 MSCN planes."""
+    Y = niqe_y(img)
+    _niqe_check_shape(1 if np.asarray(img).ndim == 2 else np.asarray(img).shape[2], *Y.shape)
+    tables = niqe_tables()
+    nh, nw = Y.shape[0] // NIQE_BLOCK, Y.shape[1] // NIQE_BLOCK
+    Y = np.ascontiguousarray(Y[:nh * NIQE_BLOCK, :nw * NIQE_BLOCK])
+    feats, planes = [], []
+    for scale in (1, 2):
+        n = niqe_mscn_host(Y, params["window"])
+        planes.append(n)
+        bs = NIQE_BLOCK // scale
+        feats.append(np.array([_niqe_block_features(n[ih * bs:(ih + 1) * bs, iw * bs:(iw + 1) * bs], tables)
+                               for iw in range(nw) for ih in range(nh)], np.float64))
+        if scale == 1:
+            t = Y / np.float32(255)
+            Y = (((t[0::2, 0::2] + t[0::2, 1::2]) + t[1::2, 0::2]) + t[1::2, 1::2]) * np.float32(0.25) * np.float32(255)
+    feats = np.concatenate(feats, axis=1)
+    return (feats, planes) if return_mscn else feats
+
+
+def niqe_from_features(feats, params):
+    """Step 6: fit a Gaussian to the feature rows and return its distance to the pristine model; NaN when fewer than 2 rows are
+    NaN-free (no covariance)."""
+    feats = np.asarray(feats, np.float64)
+    good = feats[~np.isnan(feats).any(axis=1)]
+    if good.shape[0] < 2:
+        return float("nan")
+    mu = np.nanmean(feats, axis=0)
+    cov = np.cov(good, rowvar=False)
+    d = params["mu"] - mu
+    return float(np.sqrt(d @ np.linalg.pinv((params["cov"] + cov) / 2) @ d))
+
+
+def calculate_niqe(img, params):
+    """NIQE of a uint8 RGB (H, W, 3) or grey (H, W) image on the host."""
+    return niqe_from_features(niqe_features_host(img, params), params)
+
+
+def niqe_features_device(x, params, return_mscn=False):
+    """Steps 1-5 on the GPU (csrc/niqe.hip.h) for fp32 (B, C, H, W) CUDA images in [-1, 1], read in place (unit column stride):
+    a (B, nblk, 36) float64 CPU tensor, one device-to-host copy; with ``return_mscn`` also the (B, 5/4 Hc Wc) float32 MSCN planes
+    (scale 1 then scale 2 per image) as a CUDA tensor."""
+    import torch
+    from . import lib
+    from .ucdir import _ptr, _stream_ptr
+    if not torch.is_tensor(x) or not x.is_cuda:
+        raise ValueError("niqe_device takes a tensor on the GPU")
+    if x.dtype != torch.float32:
+        raise ValueError(f"niqe_device takes fp32 images, got {x.dtype}")
+    if x.dim() == 3:
+        x = x.unsqueeze(0)
+    if x.dim() != 4 or x.shape[0] < 1:
+        raise ValueError(f"niqe_device takes (B, C, H, W) or (C, H, W) images, got {tuple(x.shape)}")
+    B, C, H, W = x.shape
+    _niqe_check_shape(C, H, W)
+    if x.stride(3) != 1:
+        raise ValueError("niqe_device: the column stride of x must be 1")
+    L = lib.load()
+    key = ("dev", x.device)
+    if key not in _niqe_tables_cache:
+        _niqe_tables_cache[key] = torch.from_numpy(niqe_tables()).to(x.device)
+    tables = _niqe_tables_cache[key]
+    nbytes = L.ucdir_niqe_workspace_bytes(B, C, H, W)
+    if nbytes < 0:
+        raise ValueError(f"niqe_device: {C} x {H} x {W} is outside what ucdir_niqe_features supports (include/ucdir_hip.h)")
+    nblk = (H // NIQE_BLOCK) * (W // NIQE_BLOCK)
+    ws = torch.empty(nbytes // 8, dtype=torch.int64, device=x.device)
+    feats = torch.empty((B, nblk, 36), dtype=torch.float64, device=x.device)
+    mscn = torch.empty((B, nblk * NIQE_BLOCK * NIQE_BLOCK * 5 // 4), dtype=torch.float32, device=x.device) if return_mscn else None
+    window = np.ascontiguousarray(params["window"], np.float64)
+    if window.shape != (7, 7):
+        raise ValueError("niqe_device: the Gaussian window must be 7 x 7")
+    lib.check(L.ucdir_niqe_features(_ptr(x), x.stride(0), x.stride(1), x.stride(2), B, C, H, W, window.ctypes.data, _ptr(tables),
+                                    _ptr(feats), _ptr(mscn) if return_mscn else None, _ptr(ws), _stream_ptr(x.device)))
+    host = feats.cpu()
+    return (host, mscn) if return_mscn else host
+
+
+def niqe_device(x, params):
+    """NIQE of the uint8 images tensor2img_u8_device makes of ``x``, (B, C, H, W) or (C, H, W) fp32 CUDA tensors in [-1, 1], with the
+    image-sized work on the GPU: a list of floats, one per image.  The 36 x 36 algebra of step 6 stays on the host."""
+    return [niqe_from_features(f, params) for f in niqe_features_device(x, params).numpy()]

@@ -117,6 +117,18 @@ class DDPM:
         sr = self.SR[self.SR.shape[0] - B:] if self.SR.dim() == 4 else self.SR
         return psnr_ssim_device(sr, self.data["HR"])
 
+    def current_niqe(self, params=None):
+        """NIQE of the images of the last ``test()``: the final SR block, scored with the image-sized work on the GPU
+        (metrics.niqe_device) on the same uint8 quantisation as ``visuals_u8``; ``params`` from metrics.load_niqe_params
+        (default: ``self.niqe_params``)."""
+        from .metrics import niqe_device
+        params = params if params is not None else getattr(self, "niqe_params", None)
+        if params is None:
+            raise ValueError("current_niqe needs the pristine-model statistics: pass params or set DDPM.niqe_params (metrics.load_niqe_params)")
+        B = self.data["SR"].shape[0]
+        sr = self.SR[self.SR.shape[0] - B:] if self.SR.dim() == 4 else self.SR
+        return niqe_device(sr, params)
+
     def load_network(self):
         """model/model.py:224-251: in val phase with EMA on, ``{prefix}_gen_ema.pth`` is loaded strict=False."""
         prefix = self.opt["path"]["resume_state"]
