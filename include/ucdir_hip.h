@@ -230,8 +230,7 @@ int64_t ucdir_workspace_bytes(const ucdir_ctx* ctx);
  * "flash": 1 = flash-attention kernel, 0 = materialised-score path (QK^T, softmax, PV as three launches),
  * -1 = environment default (UCDIR_NO_FLASH).  "splitk": 1 / 0 / -1 the same for split-K and unit splits of
  * under-filled grids (UCDIR_SPLITK).  "persist_grid": n > 0 launches the persistent kernels (akgm_ws) with n workgroups
- * instead of one per compute unit, 0 restores the default.  "wsb": 1 routes the AKGM tails of 8 / 16 channels per group
- * through akgm_ws32_kernel<8 | 16> instead of akgm_ws_kernel (tests), 0 / -1 = akgm_ws_kernel.  "convsk": 0 = 3x3 convs
+ * instead of one per compute unit, 0 restores the default.  "convsk": 0 = 3x3 convs
  * on conv3x3_halo (the round-3 dispatch), 1 = conv_sk_kernel's persistent 8-wave stream-K kind forced, 2 = its one-shot 4-wave kind
  * forced (both regardless of the size thresholds: tests), -1 = environment default (UCDIR_NO_CONV_SK; the 4-wave kind).  Unknown
  * names are an error. */

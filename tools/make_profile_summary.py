@@ -26,7 +26,7 @@ def bench_name(k):
         tm, epi, mode = int(m.group(1)), int(m.group(2)), int(m.group(3))
         return f"cgemm<{tm},akgm>" if epi == 1 else f"cgemm<{tm},std,{MODE[mode]}>"
     if "akgm_halo_kernel" in k or "akgm_halo_stage_kernel" in k:
-        return "akgm_halo"                          # <true> / <false> instantiations share one bench row
+        return "akgm_halo"                          # the two one-shot ring kernels share one bench row (profiler key 111)
     if "akgm_pre_kernel" in k:
         return "akgm_pre"
     if "akgm_ws64_kernel" in k:

@@ -80,18 +80,16 @@ __device__ __forceinline__ void akgm_tc_slice(const AkgmHP& p, int fbase, float*
     }
 }
 
-// ATT_LDS (16 / 32 channels per group: one halo chunk per workgroup, the second halo buffer is free): the per-pixel
-// modulation weights G*attw live in that buffer instead of 16 VGPRs, and the accumulators start at the fold constants
-// (as in akgm_pre.hip.h) so the epilogue needs 8 instead of 16 FMAs per output.  With 64 per group both halo buffers
-// are in use and the register version stays.
-template <bool ATT_LDS>
+// One halo chunk per workgroup leaves the second halo buffer free: the per-pixel modulation weights G*attw live in that
+// buffer instead of 16 VGPRs, and the accumulators start at the fold constants (as in akgm_pre.hip.h) so the epilogue
+// needs 8 instead of 16 FMAs per output.  With 64 per group both halo buffers hold channels: akgm_halo_stage_kernel.
 __global__ __launch_bounds__(HC_THREADS, 4) void akgm_halo_kernel(const AkgmHP p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* halo = smem;
     unsigned char* aring = smem + 2 * HC_HALO_BYTES;
     float* scal = reinterpret_cast<float*>(smem + 2 * HC_HALO_BYTES + 2 * AH_ASTAGE);
     float* tcs = scal + 32;                                          // [9][128]
-    float* attl = reinterpret_cast<float*>(halo + HC_HALO_BYTES);    // ATT_LDS: [256 px][8]
+    float* attl = reinterpret_cast<float*>(halo + HC_HALO_BYTES);    // [256 px][8] modulation weights G * attw
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // provably wave-uniform: no waterfall loops around global_load_lds
@@ -148,7 +146,7 @@ __global__ __launch_bounds__(HC_THREADS, 4) void akgm_halo_kernel(const AkgmHP p
     }
 
     // ---- per-lane pixel constants --------------------------------------------------------------------
-    int hp0[2], cls[2], goff[2];
+    int hp0[2], cls[2];
 #pragma unroll
     for (int tp = 0; tp < 2; ++tp) {
         int slot = wq * 64 + tp * 32 + (lane & 31);
@@ -159,16 +157,13 @@ __global__ __launch_bounds__(HC_THREADS, 4) void akgm_halo_kernel(const AkgmHP p
         int y = y0 + r, x = x0 + c;
         y = y < p.H ? y : p.H - 1; x = x < p.W ? x : p.W - 1;
         cls[tp] = (y == 0 ? 0 : (y == p.H - 1 ? 2 : 1)) * 3 + (x == 0 ? 0 : (x == p.W - 1 ? 2 : 1));
-        goff[tp] = (y * p.W + x) * 8;
-        if (ATT_LDS) {
-            const float* gp = p.G + (long long)b * p.g_bstride + goff[tp];
-            const float4 g0 = *reinterpret_cast<const float4*>(gp), g1 = *reinterpret_cast<const float4*>(gp + 4);
-            const float* aw = p.attw + b * 8;
-            if (wm == 0) {                   // the two row halves see the same pixels: one of them publishes G * attw
-                float* ap = attl + (wq * 64 + tp * 32 + (lane & 31)) * 8;
-                *reinterpret_cast<float4*>(ap) = make_float4(g0.x * aw[0], g0.y * aw[1], g0.z * aw[2], g0.w * aw[3]);
-                *reinterpret_cast<float4*>(ap + 4) = make_float4(g1.x * aw[4], g1.y * aw[5], g1.z * aw[6], g1.w * aw[7]);
-            }
+        const float* gp = p.G + (long long)b * p.g_bstride + (y * p.W + x) * 8;
+        const float4 g0 = *reinterpret_cast<const float4*>(gp), g1 = *reinterpret_cast<const float4*>(gp + 4);
+        const float* aw = p.attw + b * 8;
+        if (wm == 0) {                       // the two row halves see the same pixels: one of them publishes G * attw
+            float* ap = attl + (wq * 64 + tp * 32 + (lane & 31)) * 8;
+            *reinterpret_cast<float4*>(ap) = make_float4(g0.x * aw[0], g0.y * aw[1], g0.z * aw[2], g0.w * aw[3]);
+            *reinterpret_cast<float4*>(ap + 4) = make_float4(g1.x * aw[4], g1.y * aw[5], g1.z * aw[6], g1.w * aw[7]);
         }
     }
     int a_off[2], a_sw[2];
@@ -203,10 +198,9 @@ __global__ __launch_bounds__(HC_THREADS, 4) void akgm_halo_kernel(const AkgmHP p
         else { fbase = sec * cg + unit * 16; base16 = 0; Au = p.A + ((long long)sec * p.C + unit * AH_TM) * p.Kpad; }
     };
     // fold table slice of a unit, Tc[b][cls][8*fbase .. +128), DMA'd into LDS: instruction w (waves 0-4) carries classes
-    // 2w and 2w+1 (32 lanes x 16 B each).  ATT_LDS keeps two slices (the accumulators of unit u+1 start from its slice
-    // while nothing of unit u reads its own any more); the second one sits behind the modulation weights in the free halo
-    // buffer.  Without ATT_LDS the slice is read in the epilogue: one buffer, refilled after the next unit's first barrier.
-    float* tcs1 = ATT_LDS ? attl + 256 * 8 : tcs;
+    // 2w and 2w+1 (32 lanes x 16 B each).  Two slices are kept (the accumulators of unit u+1 start from its slice while
+    // unit u's is still in use); the second one sits behind the modulation weights in the free halo buffer.
+    float* tcs1 = attl + 256 * 8;
     // (own_tc: the slice is formed from the sample-independent tables by plain loads - issued and waited for IN FRONT of the weight stage's DMA
     // that follows every call, so that only an L2 round trip of two 16-byte loads is exposed - and written to the DMA's LDS addresses)
     auto issue_Tc = [&](int fbase, float* dst) {
@@ -240,23 +234,15 @@ __global__ __launch_bounds__(HC_THREADS, 4) void akgm_halo_kernel(const AkgmHP p
         int fbase, base16;
         const bf16_t* Au;
         unit_geom(unit, Au, fbase, base16);
-        const float* tcu = (ATT_LDS && (unit & 1)) ? tcs1 : tcs;
+        const float* tcu = (unit & 1) ? tcs1 : tcs;
         AH_STAMP();
         f32x16_t acc[2][2];
-        if (!ATT_LDS) {
-#pragma unroll
-            for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-                for (int tp = 0; tp < 2; ++tp)
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) acc[tm][tp][e] = 0.f;
-        }
 
         int cch = 0, sp = 0;                     // halo chunk and stage index within the chunk period
         auto kstep = [&](int s) {
             HC_WAIT(0);
             asm volatile("s_barrier" ::: "memory");          // stage gs landed; every wave is past stage gs - 1 (and past the previous unit's epilogue)
-            if (ATT_LDS && s == 0) {
+            if (s == 0) {
                 // the fold table slice has landed: start at Tc[cls(pixel)][row] (registers 8q..8q+7 of a tile = the 8 sets
                 // of feature 4*t32 + 2q + hh, original row order 8*feature + set)
 #pragma unroll
@@ -273,14 +259,13 @@ __global__ __launch_bounds__(HC_THREADS, 4) void akgm_halo_kernel(const AkgmHP p
                         }
                 }
             }
-            if (!ATT_LDS && s == 0 && unit > 0) issue_Tc(fbase, tcs);      // single slice: the previous unit's epilogue is behind the barrier
             // the next stage goes into the slot stage gs - 1 has just left: this unit's, or - across the unit boundary, so that
             // it lands under this unit's epilogue - the next unit's first one (with its fold table slice)
             if (s + 1 < nk) issue_A(Au, s + 1, (gs + 1) & 1);
             else if (unit + 1 < nunits) {
                 const bf16_t* Aun; int fbn, b16n;
                 unit_geom(unit + 1, Aun, fbn, b16n);
-                if (ATT_LDS) issue_Tc(fbn, ((unit + 1) & 1) ? tcs1 : tcs);
+                issue_Tc(fbn, ((unit + 1) & 1) ? tcs1 : tcs);
                 issue_A(Aun, 0, (gs + 1) & 1);
             }
             const unsigned char* Hb = halo + cch * HC_HALO_BYTES;
@@ -323,17 +308,8 @@ __global__ __launch_bounds__(HC_THREADS, 4) void akgm_halo_kernel(const AkgmHP p
         // defined inside the loop would occupy their registers for ALL its iterations and spill), and ahead of the next
         // unit's DMA in the in-order VMEM queue
         uint4 rv = make_uint4(0, 0, 0, 0);       // residual of this lane's store item
-        float4 gq[ATT_LDS ? 1 : 2][2];           // without ATT_LDS: G of the lane's two pixels
         if (off2 >= 0) rv = *reinterpret_cast<const uint4*>(p.res + (long long)b * p.res_bstride + off2 + fbase);
         kstep(nk - 1);
-        if (!ATT_LDS) {                          // 64 channels per group: no room for these 16 registers during a K step
-#pragma unroll
-            for (int tp = 0; tp < 2; ++tp) {
-                const float* gp = p.G + (long long)b * p.g_bstride + goff[tp];
-                gq[ATT_LDS ? 0 : tp][0] = *reinterpret_cast<const float4*>(gp);
-                gq[ATT_LDS ? 0 : tp][1] = *reinterpret_cast<const float4*>(gp + 4);
-            }
-        }
 
         AH_STAMP();
         // ---- epilogue WITHOUT LDS stage and WITHOUT barriers (see akgm_pre.hip.h): modulation sum in registers,
@@ -343,36 +319,20 @@ __global__ __launch_bounds__(HC_THREADS, 4) void akgm_halo_kernel(const AkgmHP p
 #pragma unroll
         for (int tp = 0; tp < 2; ++tp) {
             const int px = wq * 64 + tp * 32 + (lane & 31);
-            const float* tc = tcu + cls[tp] * AH_TM;
             float av[8];
-            if (ATT_LDS) {
+            {
                 const float4 a0 = *reinterpret_cast<const float4*>(attl + px * 8), a1 = *reinterpret_cast<const float4*>(attl + px * 8 + 4);
                 av[0] = a0.x; av[1] = a0.y; av[2] = a0.z; av[3] = a0.w; av[4] = a1.x; av[5] = a1.y; av[6] = a1.z; av[7] = a1.w;
-            } else {
-                const float* aw = p.attw + b * 8;
-                const float4 g0 = gq[ATT_LDS ? 0 : tp][0], g1 = gq[ATT_LDS ? 0 : tp][1];
-                av[0] = g0.x * aw[0]; av[1] = g0.y * aw[1]; av[2] = g0.z * aw[2]; av[3] = g0.w * aw[3];
-                av[4] = g1.x * aw[4]; av[5] = g1.y * aw[5]; av[6] = g1.z * aw[6]; av[7] = g1.w * aw[7];
             }
 #pragma unroll
-            for (int tm = 0; tm < 2; ++tm) {
-                const int t32 = wm * 2 + tm;
+            for (int tm = 0; tm < 2; ++tm)
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
-                    const int floc = 4 * t32 + 2 * q + hh;
-                    float sa = 0.f, sb = 0.f;
-                    if (!ATT_LDS) {
-                        const float4 c0 = *reinterpret_cast<const float4*>(tc + 8 * floc);
-                        const float4 c1 = *reinterpret_cast<const float4*>(tc + 8 * floc + 4);
-                        const float tcv[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
-#pragma unroll
-                        for (int s = 0; s < 8; ++s) sb += av[s] * tcv[s];
-                    }
+                    float sa = 0.f;
 #pragma unroll
                     for (int s = 0; s < 8; ++s) sa += av[s] * acc[tm][tp][8 * q + s];
-                    vq[tm][q][tp] = rstd * (sa + sb);
+                    vq[tm][q][tp] = rstd * sa;
                 }
-            }
         }
         float o8[8];
 #pragma unroll
@@ -422,14 +382,12 @@ __global__ __launch_bounds__(HC_THREADS, 4) void akgm_halo_kernel(const AkgmHP p
 // epilogue is a fifth of a unit, not a third.
 // ------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(HC_THREADS, 4) void akgm_halo_stage_kernel(const AkgmHP p) {
-    constexpr bool ATT_LDS = false;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* halo = smem;
     unsigned char* aring = smem + 2 * HC_HALO_BYTES;
     float* stage = reinterpret_cast<float*>(aring);                  // aliases the A ring between units
     float* scal = reinterpret_cast<float*>(smem + 2 * HC_HALO_BYTES + 2 * AH_ASTAGE);
     float* tcs = scal + 32;                                          // [9][128]
-    float* attl = reinterpret_cast<float*>(halo + HC_HALO_BYTES);    // ATT_LDS: [256 px][8]
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // provably wave-uniform: no waterfall loops around global_load_lds
@@ -492,7 +450,7 @@ __global__ __launch_bounds__(HC_THREADS, 4) void akgm_halo_stage_kernel(const Ak
 
     // ---- per-lane pixel constants --------------------------------------------------------------------
     int hp0[2], cls[2]; bool valid[2];
-    float att[ATT_LDS ? 1 : 2][8];
+    float att[2][8];
 #pragma unroll
     for (int tp = 0; tp < 2; ++tp) {
         int slot = wq * 64 + tp * 32 + (lane & 31);
@@ -507,16 +465,8 @@ __global__ __launch_bounds__(HC_THREADS, 4) void akgm_halo_stage_kernel(const Ak
         const float* gp = p.G + (long long)b * p.g_bstride + ((long long)y * p.W + x) * 8;
         const float4 g0 = *reinterpret_cast<const float4*>(gp), g1 = *reinterpret_cast<const float4*>(gp + 4);
         const float* aw = p.attw + b * 8;
-        if (ATT_LDS) {
-            if (wm == 0) {                   // the two row halves see the same pixels: one of them publishes G * attw
-                float* ap = attl + (wq * 64 + tp * 32 + (lane & 31)) * 8;
-                *reinterpret_cast<float4*>(ap) = make_float4(g0.x * aw[0], g0.y * aw[1], g0.z * aw[2], g0.w * aw[3]);
-                *reinterpret_cast<float4*>(ap + 4) = make_float4(g1.x * aw[4], g1.y * aw[5], g1.z * aw[6], g1.w * aw[7]);
-            }
-        } else {
-            att[tp][0] = g0.x * aw[0]; att[tp][1] = g0.y * aw[1]; att[tp][2] = g0.z * aw[2]; att[tp][3] = g0.w * aw[3];
-            att[tp][4] = g1.x * aw[4]; att[tp][5] = g1.y * aw[5]; att[tp][6] = g1.z * aw[6]; att[tp][7] = g1.w * aw[7];
-        }
+        att[tp][0] = g0.x * aw[0]; att[tp][1] = g0.y * aw[1]; att[tp][2] = g0.z * aw[2]; att[tp][3] = g0.w * aw[3];
+        att[tp][4] = g1.x * aw[4]; att[tp][5] = g1.y * aw[5]; att[tp][6] = g1.z * aw[6]; att[tp][7] = g1.w * aw[7];
     }
     int a_off[2], a_sw[2];
 #pragma unroll
@@ -564,36 +514,17 @@ __global__ __launch_bounds__(HC_THREADS, 4) void akgm_halo_stage_kernel(const Ak
         AH_STAMP();
         issue_A(0, 0);
         f32x16_t acc[2][2];
-        if (!ATT_LDS) {
 #pragma unroll
-            for (int tm = 0; tm < 2; ++tm)
+        for (int tm = 0; tm < 2; ++tm)
 #pragma unroll
-                for (int tp = 0; tp < 2; ++tp)
+            for (int tp = 0; tp < 2; ++tp)
 #pragma unroll
-                    for (int e = 0; e < 16; ++e) acc[tm][tp][e] = 0.f;
-        }
+                for (int e = 0; e < 16; ++e) acc[tm][tp][e] = 0.f;
 
         int cch = 0, sp = 0;                     // halo chunk and stage index within the chunk period
         for (int s = 0; s < nk; ++s) {
             HC_WAIT(0);
             asm volatile("s_barrier" ::: "memory");
-            if (ATT_LDS && s == 0) {
-                // the fold table slice has landed: start at Tc[cls(pixel)][row] (registers 8q..8q+7 of a tile = the 8 sets
-                // of feature 4*t32 + 2q + hh, original row order 8*feature + set)
-#pragma unroll
-                for (int tp = 0; tp < 2; ++tp) {
-                    const float* tc = tcs + cls[tp] * AH_TM;
-#pragma unroll
-                    for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-                        for (int q = 0; q < 2; ++q) {
-                            const float* t8 = tc + 8 * (4 * (wm * 2 + tm) + 2 * q + hh);
-                            const float4 c0 = *reinterpret_cast<const float4*>(t8), c1 = *reinterpret_cast<const float4*>(t8 + 4);
-                            acc[tm][tp][8 * q + 0] = c0.x; acc[tm][tp][8 * q + 1] = c0.y; acc[tm][tp][8 * q + 2] = c0.z; acc[tm][tp][8 * q + 3] = c0.w;
-                            acc[tm][tp][8 * q + 4] = c1.x; acc[tm][tp][8 * q + 5] = c1.y; acc[tm][tp][8 * q + 6] = c1.z; acc[tm][tp][8 * q + 7] = c1.w;
-                        }
-                }
-            }
             if (s + 1 < nk) issue_A(s + 1, (s + 1) & 1);
             const unsigned char* Hb = halo + cch * HC_HALO_BYTES;
             const unsigned char* Ab = aring + (s & 1) * AH_ASTAGE;
@@ -650,13 +581,8 @@ __global__ __launch_bounds__(HC_THREADS, 4) void akgm_halo_stage_kernel(const Ak
             const int px = wq * 64 + tp * 32 + (lane & 31);
             const float* tc = tcs + cls[tp] * AH_TM;
             float av[8];
-            if (ATT_LDS) {
-                const float4 a0 = *reinterpret_cast<const float4*>(attl + px * 8), a1 = *reinterpret_cast<const float4*>(attl + px * 8 + 4);
-                av[0] = a0.x; av[1] = a0.y; av[2] = a0.z; av[3] = a0.w; av[4] = a1.x; av[5] = a1.y; av[6] = a1.z; av[7] = a1.w;
-            } else {
 #pragma unroll
-                for (int s = 0; s < 8; ++s) av[s] = att[ATT_LDS ? 0 : tp][s];
-            }
+            for (int s = 0; s < 8; ++s) av[s] = att[tp][s];
 #pragma unroll
             for (int tm = 0; tm < 2; ++tm) {
                 const int t32 = wm * 2 + tm;
@@ -664,13 +590,11 @@ __global__ __launch_bounds__(HC_THREADS, 4) void akgm_halo_stage_kernel(const Ak
                 for (int q = 0; q < 2; ++q) {
                     const int floc = 4 * t32 + 2 * q + hh;
                     float sa = 0.f, sb = 0.f;
-                    if (!ATT_LDS) {
-                        const float4 c0 = *reinterpret_cast<const float4*>(tc + 8 * floc);
-                        const float4 c1 = *reinterpret_cast<const float4*>(tc + 8 * floc + 4);
-                        const float tcv[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
+                    const float4 c0 = *reinterpret_cast<const float4*>(tc + 8 * floc);
+                    const float4 c1 = *reinterpret_cast<const float4*>(tc + 8 * floc + 4);
+                    const float tcv[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
 #pragma unroll
-                        for (int s = 0; s < 8; ++s) sb += av[s] * tcv[s];
-                    }
+                    for (int s = 0; s < 8; ++s) sb += av[s] * tcv[s];
 #pragma unroll
                     for (int s = 0; s < 8; ++s) sa += av[s] * acc[tm][tp][8 * q + s];
                     stage[px * AH_SL + floc] = valid[tp] ? rstd * (sa + sb) : 0.f;

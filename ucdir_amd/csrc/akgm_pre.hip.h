@@ -1,38 +1,39 @@
-// AKGM tail for 8 / 16 channels per group (C = 64 / 128: the 288^2 and 144^2 levels) with the unit's
-// weights RESIDENT in LDS (gfx950).  Reference: model/ucdir.py:129-140.
+// AKGM tail for 8 channels per group (C = 64: the 288^2 level) with the unit's weights RESIDENT in LDS
+// (gfx950).  Reference: model/ucdir.py:129-140.
 //
-// At these levels a unit (128 rows x 256 pixels) has only K = 72 / 144, i.e. 20 / 36 MFMAs per wave:
-// streaming its weights through a ring (akgm_halo.hip.h) spends the time in barriers and exposed
-// load latency.  Here the packed weights are stored in HBM as the LDS image itself,
-//     [unit][k16 step j][k half][128 rows][8 bf16]            (20 KB / 36 KB per unit)
-// and DMA'd linearly (1 KB pieces) together with the halo before anything else happens:
-//   cg = 8 : both units of the workgroup (2 x 20 KB) up front; no barrier inside the K loops;
-//   cg = 16: unit 0 up front, unit 1 streams in underneath unit 0's epilogue (instantiated, not dispatched: the ring
-//            kernel of akgm_halo.hip.h measured faster there).
+// At this level a unit (128 rows x 256 pixels) has only K = 72, i.e. 20 MFMAs per wave: streaming its
+// weights through a ring (akgm_halo.hip.h) spends the time in barriers and exposed load latency.  Here
+// the packed weights are stored in HBM as the LDS image itself,
+//     [unit][k16 step j][k half][128 rows][8 bf16]            (20 KB per unit; pack_akgm_pre)
+// and DMA'd linearly (1 KB pieces) together with the halo before anything else happens: both units of
+// the workgroup (2 x 20 KB) up front; no barrier inside the K loops.  (With 16 per group the ring kernel
+// measured faster; akgm_ws_kernel<16> reads the same image layout at 36 KB per unit.)
 // A fragments are conflict-free without a swizzle (32 lanes read 32 consecutive 16-byte slots).
 // Epilogue WITHOUT LDS and WITHOUT barriers: after the modulation sum a lane holds the lower (lane < 32) or upper
 // (lane >= 32) feature pair of each 4-feature group for its two pixels; one v_permlane32_swap per value hands
 // lanes 0-31 all eight features of pixel tp = 0 and lanes 32-63 all eight of pixel tp = 1 (lane L <-> pixel
 // 64 wq + L), i.e. exactly one 16-byte residual load and one 16-byte store per lane.  The fp32 stage, its two
 // barriers per unit and the LDS round trip are gone: after the single barrier that publishes the DMA'd tiles the
-// eight waves of a workgroup never synchronise again (cg = 8).
+// eight waves of a workgroup never synchronise again.
 #pragma once
 #include "akgm_halo.hip.h"
 
+// pack_akgm_pre's image (akgm_ws_kernel<8 | 16> reads it too) and, for 8 per group, this kernel's LDS layout
 template <int CG>
 struct AkPre {
     static constexpr int NK16 = (CG == 8) ? 5 : 9;            // 16-wide k steps per unit (cg 8: two taps x 8 ch per step, tap 9 = 0)
     static constexpr int A_UNIT = NK16 * 4096;                // bytes
-    static constexpr int NA = (CG == 8) ? 2 : 1;              // resident units
+    static constexpr int NA = 2;                              // resident units
     static constexpr int OFF_A = HC_HALO_BYTES;
     static constexpr int OFF_SCAL = OFF_A + NA * A_UNIT;
     static constexpr int OFF_TCS = OFF_SCAL + 128;
     static constexpr int OFF_ATT = OFF_TCS + NA * 9 * 128 * 4; // [256 px][8] modulation weights G * attw
-    static constexpr int LDS = OFF_ATT + 256 * 8 * 4;         // 79,232 / 70,528: two workgroups per CU
+    static constexpr int LDS = OFF_ATT + 256 * 8 * 4;         // 79,232: two workgroups per CU
 };
 
 template <int CG>
 __global__ __launch_bounds__(HC_THREADS, 4) void akgm_pre_kernel(const AkgmHP p) {
+    static_assert(CG == 8, "the LDS-resident one-shot kernel serves 8 channels per group only");
     using L = AkPre<CG>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* halo = smem;
@@ -50,7 +51,7 @@ __global__ __launch_bounds__(HC_THREADS, 4) void akgm_pre_kernel(const AkgmHP p)
         const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7;
         lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
     }
-    const int nsec = p.C / 32;                                  // 32-channel chunks: 2 (C = 64) / 4 (C = 128)
+    const int nsec = p.C / 32;                                  // 32-channel chunks
     const int sec = lid % nsec;
     int tq = lid / nsec;
     const int tx = tq % p.tiles_x; tq /= p.tiles_x;
@@ -114,7 +115,7 @@ __global__ __launch_bounds__(HC_THREADS, 4) void akgm_pre_kernel(const AkgmHP p)
         if (p.own_tc) akgm_tc_slice(p, fbase, dst, wave, lane, inv_b, mean_b); else issue_Tc(fbase, dst);
     };
     tc_slice(unit0 * 16, tcs);
-    if (CG == 8) tc_slice(unit0 * 16 + 16, tcs + 9 * 128);
+    tc_slice(unit0 * 16 + 16, tcs + 9 * 128);
 
     // ---- per-lane pixel constants (K loop / phase 1) ---------------------------------------------------
     int hp0[2], cls[2];                                                // cls: border class, or -1 for a pixel outside the image / tile
@@ -162,8 +163,8 @@ __global__ __launch_bounds__(HC_THREADS, 4) void akgm_pre_kernel(const AkgmHP p)
 #pragma unroll 1
     for (int u = 0; u < 2; ++u) {
         const int fbase = (unit0 + u) * 16;
-        const unsigned char* Au = abuf + ((CG == 8) ? u * L::A_UNIT : 0);
-        const float* tcu = tcs + ((CG == 8) ? u * 9 * 128 : 0);
+        const unsigned char* Au = abuf + u * L::A_UNIT;
+        const float* tcu = tcs + u * 9 * 128;
 
         // accumulators start at the fold constants Tc[cls(pixel)][row] (akgm_tc_kernel: already divided by rstd) instead
         // of zero: registers 0..15 of a tile = features floc0, floc0 + 1 x 8 sets = 16 consecutive floats of the table
@@ -183,18 +184,13 @@ __global__ __launch_bounds__(HC_THREADS, 4) void akgm_pre_kernel(const AkgmHP p)
         }
 
         asm volatile("" : "+v"(hp0[0]), "+v"(hp0[1]));                  // no hoisting of per-step addresses out of the unit loop (spills)
-        const int ch16 = 2 * u + ((CG == 8) ? wm : hh);                // 16-byte chunk of the halo row this lane's k half reads
+        const int ch16 = 2 * u + wm;                                   // 16-byte chunk of the halo row this lane's k half reads
         __builtin_amdgcn_s_setprio(1);
         bf16x8_t af[2][2], bfr[2][2];                                   // fragments of step j live in buffer j & 1
         auto load_frags = [&](int j, int buf) {
-            int sh;
-            if (CG == 8) {
-                const int t0 = 2 * j, t1 = (2 * j + 1 > 8) ? 8 : 2 * j + 1;     // tap 9 has zero weights: read tap 8's pixels
-                const int sh0 = (t0 / 3) * hw + (t0 % 3), sh1 = (t1 / 3) * hw + (t1 % 3);
-                sh = hh ? sh1 : sh0;
-            } else {
-                sh = (j / 3) * hw + (j % 3);
-            }
+            const int t0 = 2 * j, t1 = (2 * j + 1 > 8) ? 8 : 2 * j + 1;         // tap 9 has zero weights: read tap 8's pixels
+            const int sh0 = (t0 / 3) * hw + (t0 % 3), sh1 = (t1 / 3) * hw + (t1 % 3);
+            const int sh = hh ? sh1 : sh0;
 #pragma unroll
             for (int tm = 0; tm < 2; ++tm)
                 af[buf][tm] = *reinterpret_cast<const bf16x8_t*>(Au + j * 4096 + tm * 512 + a_lane);
@@ -223,11 +219,6 @@ __global__ __launch_bounds__(HC_THREADS, 4) void akgm_pre_kernel(const AkgmHP p)
 
         uint4 rv_next = make_uint4(0, 0, 0, 0);
         if (u == 0 && off2 >= 0) rv_next = *reinterpret_cast<const uint4*>(resp + 16);
-        if (CG == 16 && u == 0) {            // unit 1's weights / fold table replace unit 0's: every wave is done reading them
-            __syncthreads();
-            issue_A(unit0 + 1, 0, 36);
-            tc_slice(fbase + 16, tcs);
-        }
         // ---- modulation sum in registers: vq[tm][q][tp] = feature 8 wm + 4 tm + 2 hh + q of pixel tp (pack_akgm_pre) --
         float vq[2][2][2];
 #pragma unroll
@@ -274,7 +265,6 @@ __global__ __launch_bounds__(HC_THREADS, 4) void akgm_pre_kernel(const AkgmHP p)
         }
         AH_STAMP();
         rv_cur = rv_next;
-        if (CG == 16 && u == 0) { HC_WAIT(0); __syncthreads(); }
     }
 #ifdef UCDIR_TIMING
     if (dbg_on) p.dbg[255] = dbg_n;

@@ -30,14 +30,10 @@ struct AkWs32 {
     static constexpr int LDS = OFF_TCS + 9 * 1024;                // 110,592
 };
 
-// CG = 32: as described above.  CG = 16 | 8 (C = 128 | 64): the workgroup owns a BLOCK of 32 features = 2 | 4 groups (the same 64
-// bytes of a pixel), wave w the features 4 w .. 4 w + 3 of the block (group w / 4 | w / 2 of it): K = 9 x 16 = 9 steps of one tap |
-// 9 x 8 (+ one zero tap) = 5 steps of two taps; everything else - tiles, staging, epilogue - is shared.
-template <int CG>
 __global__ __launch_bounds__(HC_THREADS, 2) void akgm_ws32_kernel(const AkgmHP p) {
-    constexpr int NK = (CG == 32) ? 18 : ((CG == 16) ? 9 : 5);     // k steps (CG 32: tap j / 2, channels 16 (j & 1) .. + 15)
-    constexpr int CPX = 8 * CG;                                    // channels per pixel
-    constexpr int NB = CPX / 32;                                   // 32-feature blocks
+    constexpr int NK = 18;                                         // k steps: tap j / 2, channels 16 (j & 1) .. + 15
+    constexpr int CPX = 256;                                       // channels per pixel
+    constexpr int NB = 8;                                          // groups
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hh = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -48,7 +44,7 @@ __global__ __launch_bounds__(HC_THREADS, 2) void akgm_ws32_kernel(const AkgmHP p
         const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7;
         lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
     }
-    // workgroup -> (block, range of tiles): workgroups lid, lid + NB, ... share block lid % NB
+    // workgroup -> (group, range of tiles): workgroups lid, lid + NB, ... share group lid % NB
     const int g = lid % NB, slot = lid / NB, nwg = ((int)gridDim.x - g + NB - 1) / NB;
     const int TH = p.th, NPT = TH >> 2;                            // tile rows, pixel tiles per tile
     const int tps = p.tiles_x * p.tiles_y, T = p.nbatch * tps;
@@ -93,17 +89,12 @@ __global__ __launch_bounds__(HC_THREADS, 2) void akgm_ws32_kernel(const AkgmHP p
         srel[i] = (((px >> 3) + 1) * p.Wp + (px & 7) + 1) * CPX + 32 * g + (((tid & 3) ^ ((px >> 2) & 3)) << 3);
     }
     // B fragment of k step j, pixel tile 0, buffer 0: LDS byte address (pixel tile q: + q QSTEP).
-    // CG 32: bt[t] = tap t, channel half 0; step j = tap j / 2, half j & 1: bt[j / 2] ^ 32 [j & 1]
-    // CG 16: bt[j] = tap j, the group's chunk pair 2 (w / 4) + lane half
-    // CG 8 : bt[j] = tap 2 j (lanes 0-31) | 2 j + 1 (lanes 32-63; tap 9 has zero weights: reads tap 8), the group's chunk w / 2
-    constexpr int NBT = (CG == 8) ? 5 : 9;
-    unsigned bt[NBT];
+    // bt[t] = tap t, channel half 0; step j = tap j / 2, half j & 1: bt[j / 2] ^ 32 [j & 1]
+    unsigned bt[9];
 #pragma unroll
-    for (int t = 0; t < NBT; ++t) {
-        const int tap = (CG == 8) ? ((2 * t + hh > 8) ? 8 : 2 * t + hh) : t;
-        const int chunk = (CG == 32) ? hh : ((CG == 16) ? 2 * (wave >> 2) + hh : (wave >> 1));
-        const int r = prow + tap / 3, c = pcol + tap % 3;
-        bt[t] = (r * AkWs32::PITCH + c) * 64 + ((chunk ^ fsw(r, c)) << 4);
+    for (int t = 0; t < 9; ++t) {
+        const int r = prow + t / 3, c = pcol + t % 3;
+        bt[t] = (r * AkWs32::PITCH + c) * 64 + ((hh ^ fsw(r, c)) << 4);
     }
     const unsigned tc_lane = AkWs32::OFF_TCS + 4 * 8 * (4 * wave + 2 * hh);            // + 1024 cls: this lane's 16 table entries (2 features x 8 samples)
     const unsigned att_lane = AkWs32::OFF_ATT + l31 * 32;                                // + 1024 q: this lane's pixel of pixel tile q
@@ -213,7 +204,7 @@ __global__ __launch_bounds__(HC_THREADS, 2) void akgm_ws32_kernel(const AkgmHP p
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // the fold constants; nothing of the compiler's own is queued behind this
             auto frag = [&](auto jc, bf16x8_t (&dst)[2]) {
                 constexpr int j = decltype(jc)::value;
-                const unsigned a0 = ((CG == 32) ? (bt[j >> 1] ^ ((j & 1) << 5)) : bt[j < NBT ? j : 0]) + qoff;
+                const unsigned a0 = (bt[j >> 1] ^ ((j & 1) << 5)) + qoff;
                 lds_read16_asm<0>(dst[0], a0);
                 lds_read16_asm<AkWs32::QSTEP>(dst[1], a0);
             };

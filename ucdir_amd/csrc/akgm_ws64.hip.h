@@ -177,12 +177,7 @@ __global__ __launch_bounds__(64 * NW, 2) void akgm_ws64_kernel(const AkgmHP p) {
         if (have_prev && wave < NDW) {                              // the previous tile's finished segments out
 #pragma unroll
             for (int i = 0; i < NROP; ++i) {
-#ifndef W64_ABL_NOSTORE
-                if (prev_out[i] >= 0)
-#else
-                if (prev_out[i] == -12345)
-#endif
-                {
+                if (prev_out[i] >= 0) {
                     const u32x4_t ln = *reinterpret_cast<const u32x4_t*>(smem + OFF_STAGE + (buf ^ 1) * L::STAGE + (i * 64 * NDW + tid) * 16);
                     *reinterpret_cast<u32x4_t*>(reinterpret_cast<unsigned char*>(p.out) + prev_out[i]) = ln;
                 }
@@ -222,9 +217,7 @@ __global__ __launch_bounds__(64 * NW, 2) void akgm_ws64_kernel(const AkgmHP p) {
         // order, the data is in registers by then)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         W64_STAMP();                                                // stores issued
-#ifndef W64_ABL_NODMA
         if (!last && wave < NDW) static_for<0, NOPS>([&](auto opc) { dma_op(opc, nb, nti, buf ^ 1); });
-#endif
 
         const int P0 = Wp + 1 + ti * NPX;
         const unsigned ab0 = buf * L::ATT, sb0 = buf * L::STAGE;
@@ -246,12 +239,7 @@ __global__ __launch_bounds__(64 * NW, 2) void akgm_ws64_kernel(const AkgmHP p) {
                 const int cy = (y <= 1) ? 0 : ((y >= p.H) ? 2 : 1);
                 const int cx = (x <= 1) ? 0 : ((x >= p.W) ? 2 : 1);
                 const unsigned tca = tc_lane + (cy * 3 + cx) * (128 * NW);
-#ifdef W64_ABL_NOINIT
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[tq][e] = (float)tca;
-#else
                 acc[tq] = lds_read_f32x16(smem + tca);            // (concatenated reads: no v_mov, asmops.hip.h)
-#endif
             }
             // K loop software-pipelined by hand (inline-asm fragment reads, counted lgkmcnt; see akgm_ws.hip.h): the fragments of
             // steps j + 1 and j + 2 are in flight under the two MFMAs of step j (64 matrix-core cycles < one LDS round trip)
@@ -279,9 +267,6 @@ __global__ __launch_bounds__(64 * NW, 2) void akgm_ws64_kernel(const AkgmHP p) {
             __builtin_amdgcn_s_setprio(0);
             W64_STAMP();                                            // K loop done
             // ---- modulation sum, swish, residual, statistics; the lane's two features go back into the staging slot -------------
-#ifdef W64_ABL_NOEPI
-            s1 += acc[0][0] + acc[1][5];
-#else
 #pragma unroll
             for (int tq = 0; tq < 2; ++tq) {
                 const unsigned aq = att_lane + ab0 + (qp + tq) * 1024;
@@ -303,7 +288,6 @@ __global__ __launch_bounds__(64 * NW, 2) void akgm_ws64_kernel(const AkgmHP p) {
                 v0 = valid[tq] ? v0 : 0.f; v1 = valid[tq] ? v1 : 0.f;        // border columns / positions past the sample: dropped
                 s1 += v0 + v1; s2 += v0 * v0 + v1 * v1;
             }
-#endif
 #pragma unroll
             for (int k = 0; k < 9; ++k) bt[k] += 2 * L::PSTEP;
         }

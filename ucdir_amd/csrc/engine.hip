@@ -119,7 +119,7 @@ struct AkgmW {
     bf16_t* A = nullptr; float* bias = nullptr; float* Tb = nullptr; float* Tg = nullptr;
     float* Tbb = nullptr;          // [9][8C]: bias + Tb[cls] (the persistent kernels form their Tc slices themselves, AkgmHP::own_tc)
     bf16_t* Apre = nullptr;        // cg 8 / 16: LDS image for akgm_pre.hip.h
-    bf16_t* Aws32 = nullptr;       // cg 8 / 16 / 32: A fragments of akgm_ws32_kernel<cg>
+    bf16_t* Aws32 = nullptr;       // cg 32 (C = 256): A fragments of akgm_ws32_kernel
     bf16_t* Aws64 = nullptr;       // cg 64 (C = 512): A fragments of akgm_ws64_kernel, one half group per workgroup
     int C = 0, cg = 0, Kpad = 0;
 };
@@ -167,7 +167,7 @@ static AkgmW upload_akgm(DevPool& pool, const float* wsp, const float* bsp, cons
         W.Tbb = pool.upload(tbb);
     }
     if (P.cg == 8 || P.cg == 16) W.Apre = pool.upload(pack_akgm_pre(wsp, gamma, C));
-    if (P.cg == 32 || P.cg == 16 || P.cg == 8) W.Aws32 = pool.upload(pack_akgm_ws32(wsp, gamma, C));
+    if (P.cg == 32) W.Aws32 = pool.upload(pack_akgm_ws32(wsp, gamma, C));
     if (P.cg == 64 && C == 512) W.Aws64 = pool.upload(pack_akgm_ws64(wsp, gamma, C));
     return W;
 }
@@ -319,10 +319,10 @@ static void ensure_kernel_attrs() {
     set_lds_attr(conv3x3_halo_kernel<128, false>, hc_lds_bytes<128>());
     set_lds_attr(conv3x3_halo_kernel<64, false>, hc_lds_bytes<64>());
     set_lds_attr(conv3x3_halo_kernel<64, true>, hc_lds_bytes<64>());
-    set_lds_attr(akgm_halo_stage_kernel, AH_LDS); set_lds_attr(akgm_halo_kernel<true>, AH_LDS);
+    set_lds_attr(akgm_halo_stage_kernel, AH_LDS); set_lds_attr(akgm_halo_kernel, AH_LDS);
     set_lds_attr(akgm_pre_kernel<8>, AkPre<8>::LDS);
     set_lds_attr(akgm_ws_kernel<8>, AkWs::LDS); set_lds_attr(akgm_ws_kernel<16>, AkWs::LDS);
-    set_lds_attr(akgm_ws32_kernel<32>, AkWs32::LDS); set_lds_attr(akgm_ws32_kernel<16>, AkWs32::LDS); set_lds_attr(akgm_ws32_kernel<8>, AkWs32::LDS);
+    set_lds_attr(akgm_ws32_kernel, AkWs32::LDS);
     set_lds_attr(akgm_ws64_kernel<2, 8, true>, 160 * 1024); set_lds_attr(akgm_ws64_kernel<4, 8, true>, 160 * 1024);
     set_lds_attr(qkv_ws_kernel<256>, QkvWs::LDS); set_lds_attr(qkv_ws_kernel<512>, QkvWs::LDS);
     set_lds_attr(conv_ws_kernel, CvWs::LDS);
@@ -440,10 +440,7 @@ static void launch_halo(GemmP p, hipStream_t st) {
     sd.print([](int, int n) { fprintf(stderr, "TIMING n=%d:", n); });
 }
 
-static std::atomic<bool> g_use_halo{true};
-
 // compute units of the current device (persistent kernels launch one workgroup per CU)
-static std::atomic<int> g_wsb{-1};             // ucdir_debug_flag("wsb", 1): block AKGM kernel also at 8 / 16 channels per group (tests); -1 / 0: off
 static std::atomic<int> g_persist_grid{0};     // > 0: ucdir_debug_flag("persist_grid", n) forces the grid of the persistent kernels (tests: many tiles per workgroup on small inputs)
 static int num_cus() {
     if (g_persist_grid > 0) return g_persist_grid;
@@ -705,8 +702,8 @@ static bool run_conv(const ConvW& w, int mode, ConvCall c, hipStream_t st) {
     if (c.res) { p.res = c.res->p; p.res_bstride = c.res->bstride(); p.res_ld = c.res->C; p.res_coff = 0; }
     p.out = y.p; p.out_bstride = y.bstride(); p.out_ld = y.C; p.nfeat = w.cout;
     if (c.nchw_out) { p.out = c.nchw_out; p.out_nchw = 1; p.crop_h = c.crop_h; p.crop_w = c.crop_w; }   // fp32 (B, cout, crop_h, crop_w)
-    const bool upph = g_use_halo && mode == COLS_UP && w.Aup && x0.C % 64 == 0 && !x1;
-    const bool halo = upph || (g_use_halo && mode == COLS_S1 && w.ntaps == 9 && x0.C % 64 == 0 && (!x1 || x1->C % 64 == 0));
+    const bool upph = mode == COLS_UP && w.Aup && x0.C % 64 == 0 && !x1;
+    const bool halo = upph || (mode == COLS_S1 && w.ntaps == 9 && x0.C % 64 == 0 && (!x1 || x1->C % 64 == 0));
     if (halo) {
         // tiles live on the INPUT grid for the parity-decomposed Upsample conv, on the output grid otherwise
         const int gh = upph ? x0.H : y.H, gw = upph ? x0.W : y.W;
@@ -853,10 +850,8 @@ static void run_akgm_halo(const AkgmW& w, const Act& h1, const float* G, const f
     // 32 channels per group (C = 256): one group per workgroup, TH x 8 tiles (akgm_ws32.hip.h)
     int th32 = 0;
     for (int cand : {32, 24, 16, 8}) if (y.H % cand == 0) { th32 = cand; break; }
-    // (ucdir_debug_flag("wsb", 1): the block kernel also at 8 / 16 channels per group instead of akgm_ws_kernel - tests)
-    const bool wsb_all = g_wsb > 0;
     const int nb32 = w.C / 32;
-    if (use_ws && !env().no_ws32 && w.Aws32 != nullptr && (w.cg == 32 || (wsb_all && (w.cg == 16 || w.cg == 8))) && w.C == 8 * w.cg && th32 > 0 && y.W % 8 == 0 &&
+    if (use_ws && !env().no_ws32 && w.Aws32 != nullptr && w.cg == 32 && th32 > 0 && y.W % 8 == 0 &&
         (g_persist_grid > 0 || (long long)y.B * (y.H / th32) * (y.W / 8) * nb32 >= 4LL * num_cus()))
         kind = AkgmKind::WS32;
     // 64 channels per group (C = 512: the 36^2 / 18^2 levels), akgm_ws64.hip.h: half a group per workgroup of eight waves, one per CU, the tile's
@@ -897,8 +892,7 @@ static void run_akgm_halo(const AkgmW& w, const Act& h1, const float* G, const f
             const int ntiles = y.B * p.tiles_x * p.tiles_y;
             int ncu = num_cus() / nb32 * nb32; if (ncu < nb32) ncu = nb32;
             grid = nb32 * ntiles < ncu ? nb32 * ntiles : ncu;                // one workgroup per 32-feature block per tile range
-            kernel = w.cg == 32 ? akgm_ws32_kernel<32> : w.cg == 16 ? akgm_ws32_kernel<16> : akgm_ws32_kernel<8>;
-            key = KEY_AKGM_WS32; lds = AkWs32::LDS;
+            kernel = akgm_ws32_kernel; key = KEY_AKGM_WS32; lds = AkWs32::LDS;
             break;
         }
         case AkgmKind::WS: {
@@ -916,7 +910,7 @@ static void run_akgm_halo(const AkgmW& w, const Act& h1, const float* G, const f
             break;
         }
         case AkgmKind::PRE: kernel = akgm_pre_kernel<8>; key = KEY_AKGM_PRE; lds = AkPre<8>::LDS; break;
-        case AkgmKind::HALO_ATTLDS: kernel = akgm_halo_kernel<true>; break;
+        case AkgmKind::HALO_ATTLDS: kernel = akgm_halo_kernel; break;
         case AkgmKind::HALO_STAGE: break;
     }
     if (!p.own_tc)
@@ -932,7 +926,7 @@ static void run_akgm(const AkgmW& w, const Act& h1, const float* G, const float*
                      float* tcbuf, hipStream_t st) {
     const int C = w.C;
     require(C == 64 || C % 128 == 0, "AKGM: channel count must be 64 or a multiple of 128");
-    if (g_use_halo && (w.cg == 8 || w.cg == 16 || w.cg == 32 || w.cg == 64)) { run_akgm_halo(w, h1, G, attw, res, y, tcbuf, st); return; }
+    if (w.cg == 8 || w.cg == 16 || w.cg == 32 || w.cg == 64) { run_akgm_halo(w, h1, G, attw, res, y, tcbuf, st); return; }
     require(w.Kpad != 640, "AKGM weights packed for the halo kernel");
     GemmP p; zero_gemm(p);
     const int TM = (C == 64) ? 64 : 128;
@@ -2087,7 +2081,6 @@ int32_t ucdir_debug_flag(const char* name, int32_t value) {
     require(name != nullptr, "null argument");
     if (!strcmp(name, "flash")) g_flash = value;            // attention: 1 flash kernel, 0 materialised scores, -1 environment
     else if (!strcmp(name, "splitk")) g_splitk = value;     // split-K / unit split for under-filled grids: 1 on, 0 off, -1 environment
-    else if (!strcmp(name, "wsb")) g_wsb = value;
     else if (!strcmp(name, "skmix")) g_skmix = value;         // conv_sk_kernel<1, 4, 9> with wide + short units: 1 forced at any size, 0 off, -1 environment + occupancy rule
     else if (!strcmp(name, "convsk")) g_convsk = value;       // stream-K conv: 1 forced at any size, 0 off, -1 environment + work threshold
     else if (!strcmp(name, "persist_grid")) g_persist_grid = value;   // persistent kernels: workgroups per launch (0 = one per CU)
