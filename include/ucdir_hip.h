@@ -237,7 +237,12 @@ int64_t ucdir_workspace_bytes(const ucdir_ctx* ctx);
 int32_t ucdir_debug_flag(const char* name, int32_t value);
 /* Host-side launch planning, callable without a device (tests): what = "ksplit" -> the K-split factor conv3x3_halo would use
  * for a grid of `wgs` workgroups over `nchunks` 32-channel chunks of `steps_per_chunk` K steps producing `out_elems` outputs;
- * what = "usplit" -> the unit split (1 | 2 | 4) of the 64-per-group AKGM kernel for `wgs` workgroups.  -1 on a bad name. */
+ * what = "usplit" -> the unit split (1 | 2 | 4) of the 64-per-group AKGM kernel for `wgs` workgroups;
+ * what = "tile" -> th * 1000 + tw of the pixel tile conv3x3_halo / the one-shot AKGM kernels take on a plane of
+ * (`wgs`, `nchunks`) = (H, W); what = "sk_strips" -> strips * 1000 + halo pieces per chunk of conv_sk_kernel<MW, NW> on a plane of
+ * `wgs` columns, `nchunks` = 10 MW + NW (14 | 28 | 18), 0 if no split fits; what = "last_ksplit" -> the K-split factor the
+ * latest conv3x3_halo launch of this process ran with (1 = unsplit, 0 = none yet; the other arguments are ignored: split and
+ * unsplit launches share a profiler key).  -1 on a bad name. */
 int32_t ucdir_debug_launch_plan(const char* what, int32_t wgs, int32_t nchunks, int32_t steps_per_chunk, double out_elems);
 /* Per-launch HIP-event timing of the GEMM-core kernels (bench.py's roofline leg).  While enabled,
  * every launch is bracketed by events on its stream; ucdir_profile_read synchronises the stream and

@@ -31,22 +31,29 @@ EMU_LAYER_TOL = 2e-3   # one layer of the HIP path against the oracle's bf16-emu
                        # fp32 summation order and single bf16 rounding flips.  Measured (tools/_emu_probe.py): worst layer 6.7e-4 (full SID, B = 1),
                        # 4.4e-4 (B = 4), 8.9e-4 (small configuration) - the attention blocks of the 18^2 / 36^2 levels; everything else <= 4e-4.
                        # The val shapes (tests/test_val_shapes_gpu.py: 416^2, non-square, akgm_ws64's limits, 416 x 1664): worst 5.90e-4
-                       # (mid.0, B = 1 at 416^2)
+                       # (mid.0, B = 1 at 416^2).  The smallest shapes (tests/test_small_denoiser_gpu.py: 32^2 ... 64 x 32, 33^2 ... 63 x 40,
+                       # B = 64 at 33^2; a GroupNorm over 2k - 8k values): worst 1.38e-3 (mid.0, naiveforward 3 x 32 x 64)
 TILE = (64, 32, 32)    # (channels, rows, columns) of one tile_max block; one sample per block
 # tile-local bounds (metrics() keys tile_max / elem_max) and the attention-vs-emulation bounds: each about 1.5x the worst value
 # measured on the MI355X over every case that asserts it; tests/test_tile_metric_cpu.py shows the modelled faults exceed them
-OP_TILE_TOL = 4e-3     # single operator vs torch: worst 2.61e-3 (test_conv_stream_k_with_res_conv[level4_ksplit], the res_conv output)
-OP_ELEM_TOL = 5.5e-2   # ... worst 3.65e-2 (test_akgm_block_kernel_at_narrow_groups[cg8_th8]): one bf16 step of a large output
+OP_TILE_TOL = 4e-3     # single operator vs torch: worst 2.61e-3 (test_conv_stream_k_with_res_conv[level4_ksplit], the res_conv output); planes
+                       # below one tile (tests/test_small_planes_gpu.py): 3.43e-3 (conv_sk 4-wave kind, B = 64 on 2 x 2, a 256-element block;
+                       # rel-RMS <= 2.47e-3), AKGM 2.77e-3; the tile cover (tests/test_tile_cover_gpu.py): conv 2.78e-3, AKGM 2.55e-3
+OP_ELEM_TOL = 5.5e-2   # ... worst 3.65e-2 (test_akgm_block_kernel_at_narrow_groups[cg8_th8]): one bf16 step of a large output; planes below one
+                       # tile 3.18e-2, the tile cover 3.18e-2
 EMU_TILE_TOL = 1.3e-3  # one layer vs the emulation: worst 8.84e-4 (full SID B = 1, an attention block at 36^2); B = 32: 6.3e-4,
                        # 1024^2 windows: 4.3e-4, fp16 attention windows: 4.2e-4 (tests/test_layerwise_gpu.py); the val shapes: 6.34e-4
-                       # (ups.5, B = 4 at 288 x 800), while a layer with its last 32 columns one row down (shift_last_strip) gives >= 1.41
-EMU_ELEM_TOL = 6.5e-2  # ... one element (asserted by tests/test_predictor_gpu.py): worst 4.19e-2 (conv8_2, B = 16 at 384^2); the predictor's
+                       # (ups.5, B = 4 at 288 x 800); the smallest shapes, blocks of >= EMU_TILE_MIN_BLOCK elements: 1.26e-3 (downs.11, a 4096-element
+                       # block of forward_split 2 x 63 x 40; smaller blocks: EMU_TILE_MIN_BLOCK), while a layer with its last 32 columns one row down (shift_last_strip) gives >= 1.41
+EMU_ELEM_TOL = 6.5e-2  # ... one element (asserted by tests/test_predictor_gpu.py): worst 4.19e-2 (conv8_2, B = 16 at 384^2); the denoiser's smallest
+                       # shapes: 5.54e-2 (mid.0:h1, naiveforward 3 x 32 x 64: one bf16 step of an output of ~10 RMS); the predictor's
                        # layers against its emulation: rel-RMS <= 1.04e-4, tile_max <= 3.46e-4 (all shapes; no GroupNorm to amplify rounding)
 PRED_TILE_TOL = 1e-2   # the whole predictor vs the fp32 oracle (test_predictor, 3 channels x 32 x 32 blocks): worst 6.79e-3 (B = 2, 64 x 96)
 PRED_ELEM_TOL = 6e-2   # ... worst 3.93e-2 (1 x 256^2)
-ATT_EMU_TOL = 2.5e-3   # attention vs self_attention_emu, rel-RMS of the branch: worst 1.62e-3 (C = 384, N = 4096, flash)
-ATT_EMU_TILE_TOL = 3e-3  # ... worst 1.98e-3 (C = 512, N = 1296, B = 2, flash)
-ATT_EMU_ELEM_TOL = 6e-2  # ... worst 3.90e-2 (C = 512, N = 16384, flash)
+ATT_EMU_TOL = 2.5e-3   # attention vs self_attention_emu, rel-RMS of the branch: worst 1.62e-3 (C = 384, N = 4096, flash); N = 16 ... 64
+                       # (tests/test_small_planes_gpu.py): 8.34e-4 (C = 512, N = 63, materialised, masking inputs)
+ATT_EMU_TILE_TOL = 3e-3  # ... worst 1.98e-3 (C = 512, N = 1296, B = 2, flash); N = 16 ... 64: 1.38e-3 (C = 512, N = 32, B = 3, materialised)
+ATT_EMU_ELEM_TOL = 6e-2  # ... worst 3.90e-2 (C = 512, N = 16384, flash); N = 16 ... 64: 2.32e-2 (C = 512, N = 63, flash, masking inputs)
 # the in-kernel Philox noise against oracle.philox_normal in float64 (tests/test_noise_stream_gpu.py); the kernel's __logf, v_sin_f32 and
 # v_cos_f32 are approximations, so z agrees to a few fp32 ulps of |z| <= 5.77.  tests/test_noise_stream_cpu.py shows every modelled
 # fault of the stream's statement exceeds NOISE_Z_TOL by orders of magnitude
@@ -77,7 +84,8 @@ def _st():
 def tile_metrics(d, rms):
     """Tile-local view of the difference ``d`` (B, C, H, W) against a reference of global RMS ``rms``: ``tile_max`` = max over
     blocks of one sample x TILE of sqrt(mean(d^2 over the block)) / rms (ragged edge blocks divide by their true element
-    count), ``tile_at`` = (sample, channel, row, column) of that block's first element, ``elem_max`` = max |d| / rms."""
+    count), ``tile_at`` = (sample, channel, row, column) of that block's first element, ``elem_max`` = max |d| / rms,
+    ``block`` = the elements of the tensor's largest block, min(C, 64) x min(H, 32) x min(W, 32)."""
     B, Cc, H, W = d.shape
     tc, th, tw = TILE
     nc, nh, nw = -(-Cc // tc), -(-H // th), -(-W // tw)
@@ -96,7 +104,7 @@ def tile_metrics(d, rms):
     ci, r = divmod(r, nh * nw)
     hi, wi = divmod(r, nw)
     return {"tile_max": float(tile.flatten()[i]), "tile_at": (b, ci * tc, hi * th, wi * tw),
-            "elem_max": float(d.abs().max()) / max(rms, 1e-12)}
+            "elem_max": float(d.abs().max()) / max(rms, 1e-12), "block": min(Cc, tc) * min(H, th) * min(W, tw)}
 
 
 def metrics(got, ref):
@@ -124,6 +132,24 @@ def profile_keys(L, fn):
     nr = ctypes.c_int32(0)
     ulib.check(L.ucdir_profile_read(cap, keys, ln, ms, fl, by, ctypes.byref(nr), _st()))
     return r, {int(keys[i]): int(ln[i]) for i in range(nr.value)}
+
+
+class debug_flags:
+    """Context: ucdir_debug_flag settings for the launches inside it (convsk, skmix, persist_grid, splitk, flash), put back to
+    the engine's own choice (persist_grid: 0, the others: -1) on the way out."""
+
+    def __init__(self, **flags):
+        self.flags = flags
+
+    def __enter__(self):
+        L = ulib.load()
+        for k, v in self.flags.items():
+            ulib.check(L.ucdir_debug_flag(k.encode(), v))
+
+    def __exit__(self, *exc):
+        L = ulib.load()
+        for k in self.flags:
+            ulib.check(L.ucdir_debug_flag(k.encode(), 0 if k == "persist_grid" else -1))
 
 
 def rng(seed):
@@ -353,6 +379,7 @@ def attention_emu_case(B, C, H, W, seed=0, fp16=False, flash=1, masking=False):
     e = bfr(O.self_attention_emu(sd, "a.", x, True, "fp16" if fp16 else "bf16", scores=not is_flash))
     m = metrics(dy.cpu() - x, e - x)
     m["flash"] = is_flash
+    m["keys"] = sorted(keys)
     if masking:
         m["last_share"] = last_token_share(x, sd)
     return m
@@ -395,17 +422,20 @@ class HipLayers:
                 self.controls_out[name] = metrics(self.controls[name](self[key]), bfr(y))
 
 
-def layerwise_emu_sample(dn, sd, x6, lvl, guide, b, pad, attn_dtype="bf16", controls=None):
+def layerwise_emu_sample(dn, sd, x6, lvl, guide, b, pad, attn_dtype="bf16", controls=None, eps=None):
     """Layer-wise metrics of sample ``b`` of the LAST forward of ``dn`` (x6, lvl, guide: that forward's host inputs; ``pad``:
     the forward reflect-padded them by pad32 like forward_split, else they are already multiples of 32) against the emulation
     fed with the HIP path's own activations.  Returns {layer or layer:h1: metrics}; with ``controls`` (HipLayers) the pair
-    ({layer: metrics}, {controlled layer: metrics of the wrong copy})."""
+    ({layer: metrics}, {controlled layer: metrics of the wrong copy}).  ``eps``: that forward's output (B, 3, H, W); adds
+    "eps" = the final conv on the HIP path's last activation (cropped like the forward's) against it."""
     xs, gs = x6[b:b + 1], guide[b:b + 1]
     if pad:
         ph, pw = O.pad32(x6.shape[-2]), O.pad32(x6.shape[-1])
         xs, gs = F.pad(xs, (0, pw, 0, ph), mode="reflect"), F.pad(gs, (0, pw, 0, ph), mode="reflect")
     hl = HipLayers(dn, b, controls=controls)
-    O.dy3h_naive_forward_emu(sd, xs, lvl[b:b + 1], gs, taps=hl, force=hl, attn_dtype=attn_dtype)
+    e = O.dy3h_naive_forward_emu(sd, xs, lvl[b:b + 1], gs, taps=hl, force=hl, attn_dtype=attn_dtype)
+    if eps is not None:
+        hl.out["eps"] = metrics(eps[b:b + 1], e[..., :x6.shape[-2], :x6.shape[-1]])
     return (hl.out, hl.controls_out) if controls is not None else hl.out
 
 
@@ -452,6 +482,170 @@ def ws64_prediction(cfg, B, Hc, Wc, ncu):
             h, w = Hc >> Ld.level, Wc >> Ld.level
             _, _, t, n = out.get(Ld.level, (h, w, ws64_tile(B, h, w, ncu), 0))
             out[Ld.level] = (h, w, t, n + 1)
+    return out
+
+
+def conv_sk_layout(MW, NW):
+    """Python copy of CvSk<MW, NW> (conv_sk.hip.h): positions per unit, the fixed number of halo pieces, the LDS offset of the
+    halo buffers and the workgroup's LDS limit."""
+    stage, rows, lds_tab = 8192 * MW, 128 * MW, NW == 8
+    off_ms = 4 * stage + (2 * 9 * rows * 4 if lds_tab else 0)
+    nhw = 6 if NW == 4 else (4 if MW == 2 else 7)
+    return {"NPX": 64 * (NW // MW), "NHP_MAX": NW * nhw, "OFF_H": off_ms + 64 * 8, "LDS_MAX": (160 if NW == 8 else 80) * 1024}
+
+
+def conv_sk_strips(MW, NW, W):
+    """Python copy of the engine's conv_sk_strips<MW, NW> (engine.hip, try_conv_sk_mw): (vertical strips, halo pieces per
+    chunk) of a plane of W columns - the fewest strips whose halo fits the LDS and the fixed piece count - or None."""
+    L = conv_sk_layout(MW, NW)
+    ns = 1
+    while True:
+        Ws = -(-W // ns)
+        Wpe = Ws + 1 if ns == 1 else Ws + 2
+        nhp = (L["NPX"] + 2 * Wpe + 2 + 15) // 16
+        if nhp <= L["NHP_MAX"] and L["OFF_H"] + 2 * nhp * 1024 <= L["LDS_MAX"]:
+            return ns, nhp
+        if Ws <= 8:
+            return None
+        ns += 1
+
+
+def conv_sk_strip_switches(MW, NW, max_strips=3, wmax=1024):
+    """The widths on both sides of every change of conv_sk_strips' strip count up to ``max_strips`` strips: [(W - 1, W), ...]
+    with strips(W - 1) != strips(W) and both <= max_strips."""
+    out = []
+    for W in range(9, wmax):
+        a, b = conv_sk_strips(MW, NW, W - 1), conv_sk_strips(MW, NW, W)
+        if a and b and a[0] != b[0] and max(a[0], b[0]) <= max_strips:
+            out.append((W - 1, W))
+    return out
+
+
+HALO_PX = 324          # conv_halo.hip.h, HC_HALO_PX: positions of a pixel tile's halo
+_TILE_CAND = []
+
+
+def choose_tile(H, W):
+    """Python copy of the engine's choose_tile (engine.hip): the th x tw pixel tile of conv3x3_halo, its Upsample parity
+    launches and the one-shot AKGM kernels on an H x W plane - th 1..64, tw 4..256, th tw <= 256, halo (th + 2)(tw + 2) <= 324,
+    the first candidate (th ascending, then tw) of the best slot utilisation, the same double arithmetic in the same order."""
+    if not _TILE_CAND:
+        a, b = np.repeat(np.arange(1, 65), 253), np.tile(np.arange(4, 257), 64)
+        ok = (a * b <= 256) & ((a + 2) * (b + 2) <= HALO_PX)
+        _TILE_CAND.extend([a[ok], b[ok], 1e-4 * (a[ok] + 2) * (b[ok] + 2) / 324.0])
+    a, b, pen = _TILE_CAND
+    tiles = ((H + a - 1) // a).astype(np.float64) * ((W + b - 1) // b)
+    util = float(H * W) / (tiles * 256.0) - pen
+    i = int(np.argmax(util))
+    return int(a[i]), int(b[i])
+
+
+_TILE_MAPS = {}
+
+
+def tile_map(lo=2, hi=112):
+    """{(H, W): choose_tile(H, W)} for H, W in lo..hi (memoised)."""
+    if (lo, hi) not in _TILE_MAPS:
+        _TILE_MAPS[lo, hi] = {(H, W): choose_tile(H, W) for H in range(lo, hi + 1) for W in range(lo, hi + 1)}
+    return _TILE_MAPS[lo, hi]
+
+
+def tile_plane(tile, lo=2, hi=112, admit=None):
+    """The smallest plane (H W, then H) with H, W in lo..hi on which choose_tile gives ``tile``, among those with the most axes
+    (2, 1, 0) that hold at least two tiles; ``admit``: a predicate on (H, W) the plane must meet.  None if there is none."""
+    th, tw = tile
+    n = lambda hw: (-(-hw[0] // th) >= 2) + (-(-hw[1] // tw) >= 2)
+    planes = [hw for hw, t in tile_map(lo, hi).items() if t == tile and (admit is None or admit(hw))]
+    if not planes:
+        return None
+    best = max(n(hw) for hw in planes)
+    return min((hw for hw in planes if n(hw) == best), key=lambda hw: (hw[0] * hw[1], hw))
+
+
+def tile_cover(lo=2, hi=112):
+    """A cover of the distinct pixel tiles of the planes with H, W in lo..hi: for every th that occurs the tiles with its
+    smallest and largest tw, for every tw those with its smallest and largest th, every tile whose halo has >= 300 positions
+    and every tile of exactly 256 positions.  Returns [((th, tw), (H, W))] sorted by tile; (H, W) is the smallest plane of the
+    range that yields the tile with at least two tiles along both axes, else with two along one axis, else any (tile_plane)."""
+    tm = tile_map(lo, hi)
+    tiles = sorted(set(tm.values()))
+    cover = set()
+    for th in {t[0] for t in tiles}:
+        tws = [t[1] for t in tiles if t[0] == th]
+        cover |= {(th, min(tws)), (th, max(tws))}
+    for tw in {t[1] for t in tiles}:
+        ths = [t[0] for t in tiles if t[1] == tw]
+        cover |= {(min(ths), tw), (max(ths), tw)}
+    cover |= {t for t in tiles if (t[0] + 2) * (t[1] + 2) >= 300 or t[0] * t[1] == 256}
+    return [(t, tile_plane(t, lo, hi)) for t in sorted(cover)]
+
+
+EMU_TILE_MIN_BLOCK = 4096   # EMU_TILE_TOL applies to activations whose tile_max block (metrics()["block"]) holds at least this many elements.
+                            # A block of n elements that holds the activation's largest bf16 flip has tile_max >= elem_max / sqrt(n): the flips of
+                            # the emulation against itself (2.2e-2, tests/test_small_shapes_cpu.py) are 1.4e-3 on the 256 elements of a 2 x 2 plane
+                            # and 3.5e-4 on 4096.  MI355X, the smallest shapes, blocks below 4096: worst tile_max 2.45e-3 (naiveforward
+                            # 3 x 32 x 64, a 512-element block: the flip of 5.54e-2 alone, 5.54e-2 / sqrt(512)), others 0.89 - 1.93e-3
+
+
+def emu_small_ok(m):
+    """emu_layer_ok with the block-size condition of the smallest planes: the tile-local bound only where a block holds at least
+    EMU_TILE_MIN_BLOCK elements (on a smaller plane one wrong position already moves rel_rms by orders of magnitude)."""
+    return ((not m["nan"]) and m["rel_rms"] < EMU_LAYER_TOL and m["elem_max"] < EMU_ELEM_TOL
+            and (m["block"] < EMU_TILE_MIN_BLOCK or m["tile_max"] < EMU_TILE_TOL))
+
+
+def op_ok(m, tol=4e-3):
+    """The bounds of a single-operator case (tol = OP_TOL of tests/test_hip_gpu.py): global, tile-local and element."""
+    return (not m["nan"]) and m["rel_rms"] < tol and m["tile_max"] < OP_TILE_TOL and m["elem_max"] < OP_ELEM_TOL
+
+
+class _Float64Sums:
+    """Stand-in for a module (torch / torch.nn.functional) inside the oracle whose conv2d / bmm accumulate in float64 and round
+    the result to fp32 once; everything else is the module's own."""
+
+    def __init__(self, mod):
+        self._mod = mod
+
+    def __getattr__(self, name):
+        return getattr(self._mod, name)
+
+    def conv2d(self, x, w, bias=None, *a, **k):
+        return self._mod.conv2d(x.double(), w.double(), None if bias is None else bias.double(), *a, **k).float()
+
+    def bmm(self, a, b):
+        return self._mod.bmm(a.double(), b.double()).float()
+
+
+class emu_float64_sums:
+    """Context: the oracle's emulation modes with a second summation order - every conv and batched matrix product summed in
+    float64 and rounded to fp32 once (the exactly-rounded sum) instead of torch's fp32 accumulation.  The rounding points of the
+    numerics plan stay where they are."""
+
+    def __enter__(self):
+        self._saved = (O.F, O.torch)
+        O.F, O.torch = _Float64Sums(F), _Float64Sums(torch)
+
+    def __exit__(self, *exc):
+        O.F, O.torch = self._saved
+
+
+def emu_self_comparison(sd, cfg, B, H, W, levels, seed):
+    """Two summation orders of the emulation on the same inputs, layer by layer as layerwise_emu_case compares the HIP path with
+    it: one forward stores its activations as bf16; then every layer is evaluated on those stored activations (teacher forcing)
+    once with torch's fp32 sums - the role of the HIP path - and once with float64 sums.  {activation | "eps": metrics}."""
+    cond, guide, x_t = map(torch.from_numpy, synth_inputs(B, H, W, seed=seed))
+    lvl = torch.tensor(levels, dtype=torch.float32).view(B, 1)
+    x6 = torch.cat([cond, x_t], 1)
+    first = {}
+    O.dy3h_naive_forward_emu(sd, x6, lvl, guide, taps=first)
+    force = {k: bfr(v) for k, v in first.items()}
+    t32, t64 = {}, {}
+    e32 = O.dy3h_naive_forward_emu(sd, x6, lvl, guide, taps=t32, force=force)
+    with emu_float64_sums():
+        e64 = O.dy3h_naive_forward_emu(sd, x6, lvl, guide, taps=t64, force=force)
+    out = {"eps": metrics(e32, e64)}
+    for k in force:
+        out[k[len("denoise_fn."):]] = metrics(bfr(t32[k]), bfr(t64[k]))
     return out
 
 

@@ -149,8 +149,8 @@ def test_duplicate_last_key_passes_the_old_attention_assertion(shape, seen):
     assert (rel > ATT_TOL) == seen, rel
 
 
-@pytest.mark.parametrize("shape", [(1, 128, 5, 13), (1, 512, 11, 29), (2, 256, 11, 35), (1, 384, 1, 127)],
-                         ids=["N65", "N319", "N385", "N127"])
+@pytest.mark.parametrize("shape", [(1, 128, 5, 13), (1, 512, 11, 29), (2, 256, 11, 35), (1, 384, 1, 127), (1, 512, 4, 4), (1, 512, 4, 12)],
+                         ids=["N65", "N319", "N385", "N127", "N16", "N48"])
 def test_duplicate_last_key_fails_on_masking_inputs(shape):
     """masking_attention_inputs: the last key holds ~40 % of every row's mass, so one more copy of it moves every row by
     > 10 %: the attention tests' bounds fail everywhere, while the correct emulation passes them."""
@@ -168,6 +168,61 @@ def test_duplicate_last_key_fails_on_masking_inputs(shape):
     e = good - x
     row_err = float((e[..., -1] - e[..., -2]).pow(2).mean().sqrt() / e.pow(2).mean().sqrt())
     assert row_err > 0.1, row_err
+
+
+@pytest.mark.parametrize("hw", [(2, 2), (4, 4)], ids=["2x2", "4x4"])
+def test_position_from_the_neighbouring_sample_fails_on_tiny_planes(hw):
+    """The fault of a batch-flattened unit that mis-assigns a sample (tests/test_small_planes_gpu.py, the B = 64 forward of
+    tests/test_small_denoiser_gpu.py): on a 512-channel plane of 2 x 2 | 4 x 4, B = 64, ONE position of sample 10 holds the
+    values of sample 11.  A block of such a plane has 256 | 1024 elements: OP_TILE_TOL applies and
+    fails; EMU_TILE_TOL does not apply (< EMU_TILE_MIN_BLOCK), and the layer bound and the element bound fail instead - the
+    block-size condition hides nothing, because one of 256 | 1024 positions already moves the layer's rel-RMS by 4 - 9 %."""
+    H, W = hw
+    x, wb, got, ref, emu = _conv_pair(64, 512, 512, H, W, seed=8)
+    ref_e = C.bfr(emu.float())
+    ok_op, ok_emu = C.metrics(got, ref), C.metrics(got, ref_e)
+    assert C.op_ok(ok_op) and C.emu_small_ok(ok_emu), (ok_op, ok_emu)
+    assert ok_op["block"] == 64 * H * W < C.EMU_TILE_MIN_BLOCK
+    bad = got.clone()
+    bad[10, :, H - 1, W - 1] = got[11, :, H - 1, W - 1]
+    mo, me = C.metrics(bad, ref), C.metrics(bad, ref_e)
+    print(hw, "one position from the next sample:", mo, me)
+    assert not C.op_ok(mo) and not C.emu_small_ok(me)
+    assert mo["rel_rms"] > 5 * 4e-3 and mo["tile_max"] > 50 * C.OP_TILE_TOL and mo["elem_max"] > C.OP_ELEM_TOL, mo
+    assert mo["tile_at"][0] == 10, mo
+    assert me["rel_rms"] > 10 * C.EMU_LAYER_TOL and me["elem_max"] > C.EMU_ELEM_TOL, me
+
+
+def _cover_sample():
+    cover = C.tile_cover(2, 112)
+    limit = [c for c in cover if (c[0][0] + 2) * (c[0][1] + 2) == C.HALO_PX]
+    return sorted(set(limit + cover[::10]))
+
+
+@pytest.mark.parametrize("case", _cover_sample(), ids=lambda c: f"t{c[0][0]}x{c[0][1]}_p{c[1][0]}x{c[1][1]}")
+def test_tile_shape_faults_fail_on_the_covers_planes(case):
+    """The faults the tile sweep (tests/test_tile_cover_gpu.py) is there to catch, on the plane it runs for a tile th x tw - the
+    eight tiles at the halo limit and every tenth tile of the cover: the plane's second tile column stored one row down (a
+    slot -> (row, column) decode off by the tile width), and the plane's last column left zero (a ragged store masked one
+    column early).  The shift applies where the plane has a second tile column (W > tw); a single-tile plane of the cover
+    runs the zero column alone.  Each fails the global, the tile-local and the element bound of the sweep; the correct output passes."""
+    (th, tw), (H, W) = case
+    x, wb, got, ref, emu = _conv_pair(2, 64, 64, H, W, seed=9)
+    ok = C.metrics(got, ref)
+    assert C.op_ok(ok), ok
+    faults = {}
+    if W > tw and H > 1:
+        y = got.clone()
+        y[..., 1:, tw:2 * tw] = got[..., :-1, tw:2 * tw]
+        faults["second_tile_column_one_row_down"] = y
+    y = got.clone()
+    y[..., W - 1] = 0
+    faults["last_column_zero"] = y
+    for name, y in faults.items():
+        m = C.metrics(y, ref)
+        print(case, name, m)
+        assert not C.op_ok(m), (name, m)
+        assert m["rel_rms"] > 10 * 4e-3 and m["tile_max"] > 10 * C.OP_TILE_TOL and m["elem_max"] > C.OP_ELEM_TOL, (name, m)
 
 
 def test_tile_metric_ragged_blocks_and_determinism():

@@ -423,9 +423,11 @@ static void choose_tile(int H, int W, int& th, int& tw) {
     memo[{H, W}] = {th, tw};
 }
 
+static std::atomic<int> g_last_ksplit{0};      // K splits of the latest conv3x3_halo launch (ucdir_debug_launch_plan("last_ksplit"): tests pin the split, the key does not show it)
 template <int TM, bool DUAL = false>
 static void launch_halo(GemmP p, hipStream_t st) {
     const int ks = p.ksplit > 1 ? p.ksplit : 1;
+    g_last_ksplit = ks;
     const int nblk = p.nbatch * p.tiles_x * p.tiles_y * p.rowtiles * (p.up_phase ? 4 : 1) * ks + p.alt_blocks;
     ProfEntry e = gemm_entry((TM == 128 ? KEY_HALO128 : KEY_HALO64) + (p.up_phase ? KEY_HALO_UP : 0) + (DUAL ? KEY_HALO_DUAL : 0), p, EPI_STD, p.cg);
     if (p.alt_blocks) add_res_rider(e, p);
@@ -520,6 +522,19 @@ struct ConvCall {
     float* nchw_out = nullptr; int crop_h = 0, crop_w = 0;     // fp32 (B, cout, crop_h, crop_w) output instead of y
     bool did_res = false;                                      // ... and whether the launch produced it
 };
+// vertical strips of a plane of W columns: the fewest whose halo (NPX + 2 (Ws + 2) + 2 positions of 64 bytes, two buffers) fits the workgroup's LDS and
+// the kernel's fixed number of halo pieces.  Shared borders (conv_sk.hip.h, ConvSkP): W + 1 columns when the image is one strip.  false: no split fits
+template <int MW, int NW>
+static bool conv_sk_strips(int W, int& ns, int& Ws, int& Wpe, int& nhp) {
+    using L = CvSk<MW, NW>;
+    for (ns = 1;; ++ns) {
+        Ws = (W + ns - 1) / ns;
+        Wpe = ns == 1 ? Ws + 1 : Ws + 2;
+        nhp = (L::NPX + 2 * Wpe + 2 + 15) / 16;
+        if (nhp <= L::NHP_MAX && L::lds_bytes(nhp) <= L::LDS_MAX) return true;
+        if (Ws <= 8) return false;
+    }
+}
 template <int MW, int NW>
 static bool try_conv_sk_mw(const ConvW& w, ConvCall& c, bool upph, hipStream_t st, int mode) {
     using L = CvSk<MW, NW>;
@@ -530,17 +545,9 @@ static bool try_conv_sk_mw(const ConvW& w, ConvCall& c, bool upph, hipStream_t s
     const int H = x0.H, W = x0.W, Wp = W + 2, Hp = H + 2, B = x0.B;
     if (B > L::MAXB) return false;
     const int NPX = L::NPX;
-    // vertical strips: the fewest whose halo (NPX + 2 (Ws + 2) + 2 positions of 64 bytes, two buffers) fits the workgroup's LDS and the
-    // kernel's fixed number of halo pieces
-    // shared borders (conv_sk.hip.h, ConvSkP): H + 1 rows per (sample, strip), W + 1 columns when the image is one strip
+    // vertical strips (conv_sk_strips); shared borders (conv_sk.hip.h, ConvSkP): H + 1 rows per (sample, strip)
     int ns = 1, Ws = W, nhp = 0, Wpe = W + 2;
-    for (;; ++ns) {
-        Ws = (W + ns - 1) / ns;
-        Wpe = ns == 1 ? Ws + 1 : Ws + 2;
-        nhp = (NPX + 2 * Wpe + 2 + 15) / 16;
-        if (nhp <= L::NHP_MAX && L::lds_bytes(nhp) <= L::LDS_MAX) break;
-        if (Ws <= 8) return false;
-    }
+    if (!conv_sk_strips<MW, NW>(W, ns, Ws, Wpe, nhp)) return false;
     const int HpWpe = (H + 1) * Wpe;
     const long long npos = (long long)B * ns * HpWpe;
     if ((long long)B * Hp * Wp * (long long)(cin > y.C ? cin : y.C) * (upph ? 4 : 1) >= (1LL << 31) || npos >= (1LL << 30)) return false;   // 32-bit offsets in the kernel
@@ -1368,14 +1375,21 @@ struct ActPlanner {
 };
 
 static void plan_shapes(ucdir_ctx* c, int B, int H, int W, int pad_mode) {
+    // checked before any state changes, as predictor_plan does: a rejected shape must leave the last plan intact (ucdir_prepare_guide
+    // compares against c->B / H / W / pad_mode, so a half-applied plan would make the next call with the same shape skip re-planning
+    // and launch on an empty plan)
+    const int nlev = c->cfg.n_mults;
+    const int Hc = pad_mode ? (H / 32 + 1) * 32 : H, Wc = pad_mode ? (W / 32 + 1) * 32 : W;
+    require(B >= 1 && H >= 1 && W >= 1, "B, H, W must be >= 1");
+    require(!pad_mode || (H >= 33 && W >= 33), "H, W must be >= 33 (reflect pad)");
+    require(Hc % (1 << (nlev - 1)) == 0 && Wc % (1 << (nlev - 1)) == 0, "compute size must be divisible by 2^(levels-1)");
+    // no kernel was written for a plane with a side of 1 (halo rows, border classes and the linear tiles all assume H, W >= 2)
+    require(Hc >= (2 << (nlev - 1)) && Wc >= (2 << (nlev - 1)), "compute size must be at least 2^levels (the deepest planes need 2 x 2 positions)");
     c->apool.release();
     if (!c->splitk) HIPC(hipMalloc((void**)&c->splitk, SCRATCH_BYTES));   // (planning never runs under a stream capture)
     c->rt.assign(c->layers.size(), LayerRT());
     c->B = B; c->H = H; c->W = W; c->pad_mode = pad_mode;
-    if (pad_mode) { c->Hc = (H / 32 + 1) * 32; c->Wc = (W / 32 + 1) * 32; require(H >= 33 && W >= 33, "H, W must be >= 33 (reflect pad)"); }
-    else { c->Hc = H; c->Wc = W; }
-    const int nlev = c->cfg.n_mults;
-    require(c->Hc % (1 << (nlev - 1)) == 0 && c->Wc % (1 << (nlev - 1)) == 0, "compute size must be divisible by 2^(levels-1)");
+    c->Hc = Hc; c->Wc = Wc;
     c->acts_reused = !env().keep_acts && (long long)c->Hc * c->Wc > 512LL * 512;
     ActPlanner ap{c->apool, B, c->acts_reused, {}};
     int maxN = 0, attC = 0;
@@ -2094,6 +2108,23 @@ int32_t ucdir_debug_launch_plan(const char* what, int32_t wgs, int32_t nchunks, 
     try {
         if (!strcmp(what, "ksplit")) return choose_ksplit(wgs, nchunks, steps_per_chunk, out_elems);
         if (!strcmp(what, "usplit")) return choose_usplit(wgs);
+        if (!strcmp(what, "last_ksplit")) return g_last_ksplit;      // what the latest conv3x3_halo launch of this process ran with (0: none yet)
+        if (!strcmp(what, "tile")) {          // the pixel tile of an H x W plane, (wgs, nchunks) = (H, W): th * 1000 + tw
+            if (wgs < 1 || nchunks < 1) return -1;
+            int th = 0, tw = 0;
+            choose_tile(wgs, nchunks, th, tw);
+            return th * 1000 + tw;
+        }
+        if (!strcmp(what, "sk_strips")) {     // conv_sk's vertical strips of a plane of `wgs` columns, nchunks = 10 MW + NW (14 | 28 | 18): strips * 1000 + halo pieces, 0 if none fits
+            if (wgs < 1) return -1;
+            int ns = 0, Ws = 0, Wpe = 0, nhp = 0;
+            bool ok;
+            if (nchunks == 14) ok = conv_sk_strips<1, 4>(wgs, ns, Ws, Wpe, nhp);
+            else if (nchunks == 28) ok = conv_sk_strips<2, 8>(wgs, ns, Ws, Wpe, nhp);
+            else if (nchunks == 18) ok = conv_sk_strips<1, 8>(wgs, ns, Ws, Wpe, nhp);
+            else return -1;
+            return ok ? ns * 1000 + nhp : 0;
+        }
     } catch (...) {}
     return -1;
 }
