@@ -27,7 +27,10 @@
  *     thread's current HIP device before it returns; ucdir_sampler_step runs on the device that
  *     owns x_t; the single-operator test entry points (ucdir_op_*) use the current device;
  *   - the handles of one device share a 64 MiB split-K scratch: enqueue their work on ONE stream (as the sampler does:
- *     predictor, then 50 x denoiser), or order the streams yourself.
+ *     predictor, then 50 x denoiser), or order the streams yourself;
+ *   - the image entry points of the val loop take no handle and allocate nothing (the caller brings the workspace): image
+ *     metrics, NIQE features, the JPEG round trip, resampling, and the baseline JPEG encoder - ucdir_jpeg_encode_workspace_bytes,
+ *     ucdir_jpeg_encode_bound (size queries), ucdir_jpeg_encode_header (host only, no device needed), ucdir_jpeg_encode.
  */
 #ifndef UCDIR_HIP_H
 #define UCDIR_HIP_H
@@ -179,6 +182,25 @@ int32_t ucdir_image_metrics(const float* a, int64_t a_sn, int64_t a_sc, int64_t 
 int64_t ucdir_jpeg_roundtrip_workspace_bytes(int32_t B, int32_t H, int32_t W);
 int32_t ucdir_jpeg_roundtrip(const uint8_t* in, uint8_t* out, int32_t B, int32_t H, int32_t W,
                              int32_t quality, int32_t bgr, void* workspace, void* stream);
+
+/* Baseline JPEG encoder of the val loop's image files (additive in ABI 5; csrc/jpeg_encode.hip.h): the bytes of the file Pillow's
+ * Image.save(JPEG, quality, subsampling) writes - SOI, JFIF APP0, two DQT, SOF0, the four Annex K DHT, SOS, one interleaved scan
+ * with byte stuffing, EOI; no restart markers, no optimised tables.  in: (B, H, W, 3) uint8, HWC, contiguous, H and W from 1 to
+ * 65535 and at most 2^21 blocks per image (8 x 8 blocks of all three components; 4:4:4 reaches that at about 44 megapixels).
+ * quality 1..100; subsampling 0 (4:4:4) or 2 (4:2:0, libjpeg's default); bgr != 0: channel 0 is B and channel 2 is R.
+ *   ucdir_jpeg_encode_workspace_bytes  size of the device workspace (16-byte aligned), -1 on a bad shape or subsampling.
+ *   ucdir_jpeg_encode_bound            bytes per image slot of `out`, header and EOI included, -1 likewise: 623 + 2 ceil(1660 nblk
+ *                                      / 8) + 2, from the longest codes a block can take (1660 bits) and stuffing that at most
+ *                                      doubles the scan.
+ *   ucdir_jpeg_encode_header           host only: writes SOI .. SOS (623 bytes) into out[cap], returns the count, -1 on error.
+ *   ucdir_jpeg_encode                  out: (B, bound) bytes, image n's file at out + n * bound; lengths: B int32 on the device,
+ *                                      the file sizes (-1: the file would pass the bound and nothing was written).  Bytes beyond
+ *                                      a file's length are undefined.  Asynchronous on `stream`, no allocation. */
+int64_t ucdir_jpeg_encode_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t subsampling);
+int64_t ucdir_jpeg_encode_bound(int32_t H, int32_t W, int32_t subsampling);
+int32_t ucdir_jpeg_encode_header(int32_t H, int32_t W, int32_t quality, int32_t subsampling, uint8_t* out, int32_t cap);
+int32_t ucdir_jpeg_encode(const uint8_t* in, uint8_t* out, int32_t* lengths, int32_t B, int32_t H, int32_t W,
+                          int32_t quality, int32_t subsampling, int32_t bgr, void* workspace, void* stream);
 
 /* Pillow-exact image resampling of the 4x super-resolution val task (additive in ABI 5; the reference degrades every HR crop with
  * PIL.Image.resize(..., BICUBIC), data/LRHR_dataset.py:385-443): byte for byte what PIL.Image.resize makes of an 8-bit RGB image.

@@ -95,6 +95,9 @@ def make_parser():
     parser.add_argument("--ddim-eta", type=float, default=None, help="ddim noise scale (0: deterministic, 1: the reference's setting)")
     parser.add_argument("--metrics-device", choices=["cpu", "gpu"], default="cpu",
                         help="score PSNR / SSIM on the host (numpy / scipy) or on the GPU (HIP kernel, the same uint8 images)")
+    parser.add_argument("--jpeg-device", choices=["cpu", "gpu"], default="cpu",
+                        help="write the sr / hr / lr / inf JPEGs with Pillow on the host or encode them on the GPU (HIP baseline encoder, "
+                             "the same bytes)")
     parser.add_argument("--niqe", action="store_true",
                         help="also score the restored images with NIQE, the no-reference score of the reference's eval1.py")
     parser.add_argument("--niqe-params", type=str, default="./metric/niqe_pris_params.npz",
@@ -176,14 +179,22 @@ def main(argv=None):
         name = opt["name"]
         dev_scores = diffusion.current_metrics() if args.metrics_device == "gpu" else None
         dev_niqe = diffusion.current_niqe() if args.niqe and args.metrics_device == "gpu" else None
+        jpgs = diffusion.visuals_jpeg() if args.jpeg_device == "gpu" else None      # the four files of every image, as bytes
+        need_u8 = jpgs is None or dev_scores is None or (args.niqe and dev_niqe is None)
         for j, (i, _, _) in enumerate(group):
             fname = os.path.splitext(os.path.basename(val_set.sr_path[i]))[0]
-            vis = diffusion.visuals_u8(j)
-            hr_img, lr_img, fake_img, sr_img = vis["HR"], vis["LR"], vis["INF"], vis["SR"]
-            Metrics.save_jpg(sr_img, "{}/{}_{}_sr.png".format(result_path, fname, name))
-            Metrics.save_jpg(hr_img, "{}/{}_{}_hr.png".format(result_path, fname, name))
-            Metrics.save_jpg(lr_img, "{}/{}_{}_lr.png".format(result_path, fname, name))
-            Metrics.save_jpg(fake_img, "{}/{}_{}_inf.png".format(result_path, fname, name))
+            if need_u8:                                           # the uint8 images cross PCIe for Pillow or for host scoring only
+                vis = diffusion.visuals_u8(j)
+                hr_img, lr_img, fake_img, sr_img = vis["HR"], vis["LR"], vis["INF"], vis["SR"]
+            if jpgs is not None:
+                for key, tag in (("SR", "sr"), ("HR", "hr"), ("LR", "lr"), ("INF", "inf")):
+                    with open("{}/{}_{}_{}.jpg".format(result_path, fname, name, tag), "wb") as f:
+                        f.write(jpgs[j][key])
+            else:
+                Metrics.save_jpg(sr_img, "{}/{}_{}_sr.png".format(result_path, fname, name))
+                Metrics.save_jpg(hr_img, "{}/{}_{}_hr.png".format(result_path, fname, name))
+                Metrics.save_jpg(lr_img, "{}/{}_{}_lr.png".format(result_path, fname, name))
+                Metrics.save_jpg(fake_img, "{}/{}_{}_inf.png".format(result_path, fname, name))
             if dev_scores is not None:
                 tot_psnr += dev_scores[0][j]
                 tot_ssim += dev_scores[1][j]

@@ -32,6 +32,7 @@
 #include "fewstep.hip.h"
 #include "image_metrics.hip.h"
 #include "jpeg_roundtrip.hip.h"
+#include "jpeg_encode.hip.h"
 #include "resample.hip.h"
 #include "niqe.hip.h"
 #include "pack.h"
@@ -1831,6 +1832,22 @@ int32_t ucdir_image_metrics(const float* a, int64_t a_sn, int64_t a_sc, int64_t 
     API_END
 }
 
+// Annex K quantisation tables with IJG quality scaling (jcparam.c jpeg_quality_scaling + jpeg_add_quant_table, force_baseline),
+// natural order
+static void jpeg_quant_tables(int quality, int (*q)[64]) {
+    static const int std_luma[64] = {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56,
+                                     14, 17, 22, 29, 51, 87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92,
+                                     49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
+    static const int std_chroma4[16] = {17, 18, 24, 47, 18, 21, 26, 66, 24, 26, 56, 99, 47, 66, 99, 99};
+    const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+    for (int i = 0; i < 64; ++i) {
+        const int r = i >> 3, c = i & 7;
+        const int sc = (r < 4 && c < 4) ? std_chroma4[r * 4 + c] : 99;
+        q[0][i] = std::min(std::max((std_luma[i] * scale + 50) / 100, 1), 255);
+        q[1][i] = std::min(std::max((sc * scale + 50) / 100, 1), 255);
+    }
+}
+
 // JPEG round trip of the JPEG-restoration val task (csrc/jpeg_roundtrip.hip.h): the Y plane of the 16-padded image and two half-size
 // chroma planes per image
 int64_t ucdir_jpeg_roundtrip_workspace_bytes(int32_t B, int32_t H, int32_t W) {
@@ -1858,19 +1875,8 @@ int32_t ucdir_jpeg_roundtrip(const uint8_t* in, uint8_t* out, int32_t B, int32_t
         HIPC(hipPointerGetAttributes(&po, others[i]));
         require(po.type == hipMemoryTypeDevice && po.device == pa.device, w + ": " + names[i] + " must live on the device of in");
     }
-    // Annex K tables with IJG quality scaling (jcparam.c jpeg_quality_scaling + jpeg_add_quant_table, force_baseline)
-    static const int std_luma[64] = {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56,
-                                     14, 17, 22, 29, 51, 87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92,
-                                     49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
-    static const int std_chroma4[16] = {17, 18, 24, 47, 18, 21, 26, 66, 24, 26, 56, 99, 47, 66, 99, 99};
-    const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
     JpegQuant qt;
-    for (int i = 0; i < 64; ++i) {
-        const int r = i >> 3, c = i & 7;
-        const int sc = (r < 4 && c < 4) ? std_chroma4[r * 4 + c] : 99;
-        qt.q[0][i] = std::min(std::max((std_luma[i] * scale + 50) / 100, 1), 255);
-        qt.q[1][i] = std::min(std::max((sc * scale + 50) / 100, 1), 255);
-    }
+    jpeg_quant_tables(quality, qt.q);
     DevGuard dg(pa.device);
     const long long nmcu = (long long)B * ((H + 15) / 16) * ((W + 15) / 16);
     hipLaunchKernelGGL(jpeg_mcu_kernel, dim3((unsigned)((nmcu + JPEG_MCUS_PER_WG - 1) / JPEG_MCUS_PER_WG)), dim3(256), 0,
@@ -1879,6 +1885,133 @@ int32_t ucdir_jpeg_roundtrip(const uint8_t* in, uint8_t* out, int32_t B, int32_t
     const long long npix = (long long)B * H * W;
     hipLaunchKernelGGL(jpeg_upsample_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        (const unsigned char*)workspace, out, B, H, W, bgr ? 1 : 0);
+    HIPC(hipGetLastError());
+    API_END
+}
+
+// Baseline JPEG encoder of the val loop's files (csrc/jpeg_encode.hip.h).  Workspace, every part 16-byte aligned: the
+// zigzag coefficients, per-block and per-group bit offsets, per-image bit totals, per-chunk 0xFF counts, the unstuffed bitstream.
+struct JpegEncLayout {
+    int64_t nblk, ngrp, rawcap, nchunk;                   // blocks and groups per image, stream words and chunks per image
+    int64_t coef, boff, part, totbits, ffpart, raw, bytes;
+};
+
+static const char* jpeg_encode_check(int32_t B, int32_t H, int32_t W, int32_t sub) {
+    if (sub != 0 && sub != 2) return "unknown subsampling (0: 4:4:4, 2: 4:2:0)";
+    if (B < 1 || H < 1 || W < 1) return "bad shape (B, H and W at least 1)";
+    if (B > 65535) return "more than 65535 images";
+    if (H > 65535 || W > 65535) return "sides above 65535 do not fit a JPEG frame header";
+    if (jpeg_enc::blocks_per_image(H, W, sub) > jpeg_enc::MAX_BLOCKS) return "more than 2^21 blocks per image (32-bit bit offsets)";
+    return nullptr;
+}
+
+static JpegEncLayout jpeg_encode_layout(int32_t B, int32_t H, int32_t W, int32_t sub) {
+    JpegEncLayout l;
+    auto up16 = [](int64_t v) { return (v + 15) / 16 * 16; };
+    l.nblk = jpeg_enc::blocks_per_image(H, W, sub);
+    l.ngrp = (l.nblk + JPEG_ENC_GROUP - 1) / JPEG_ENC_GROUP;
+    l.rawcap = jpeg_enc::raw_cap_words(l.nblk);
+    l.nchunk = (l.rawcap * 4 + JPEG_ENC_CHUNK - 1) / JPEG_ENC_CHUNK;
+    l.coef = 0;
+    l.boff = l.coef + up16((int64_t)B * l.nblk * 128);
+    l.part = l.boff + up16((int64_t)B * l.nblk * 4);
+    l.totbits = l.part + up16((int64_t)B * l.ngrp * 4);
+    l.ffpart = l.totbits + up16((int64_t)B * 4);
+    l.raw = l.ffpart + up16((int64_t)B * l.nchunk * 4);
+    l.bytes = l.raw + (int64_t)B * l.rawcap * 4;
+    return l;
+}
+
+int64_t ucdir_jpeg_encode_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t subsampling) {
+    if (jpeg_encode_check(B, H, W, subsampling)) return -1;
+    return jpeg_encode_layout(B, H, W, subsampling).bytes;
+}
+
+int64_t ucdir_jpeg_encode_bound(int32_t H, int32_t W, int32_t subsampling) {
+    if (jpeg_encode_check(1, H, W, subsampling)) return -1;
+    const int64_t stream = (jpeg_enc::blocks_per_image(H, W, subsampling) * jpeg_enc::MAX_BLOCK_BITS + 7) / 8;
+    return jpeg_enc::HEADER_BYTES + 2 * stream + 2;
+}
+
+int32_t ucdir_jpeg_encode_header(int32_t H, int32_t W, int32_t quality, int32_t subsampling, uint8_t* out, int32_t cap) {
+    try {
+        const std::string w("ucdir_jpeg_encode_header");
+        require(quality >= 1 && quality <= 100, w + ": quality must lie in 1..100");
+        const char* bad = jpeg_encode_check(1, H, W, subsampling);
+        require(!bad, w + ": " + (bad ? bad : ""));
+        require(out, w + ": null argument");
+        require(cap >= jpeg_enc::HEADER_BYTES, w + ": cap is below the 623 bytes of the header");
+        int q[2][64];
+        jpeg_quant_tables(quality, q);
+        return jpeg_enc::write_header(H, W, subsampling, q, out);
+    } catch (const std::exception& e) {
+        g_err = e.what();
+        return -1;
+    }
+}
+
+int32_t ucdir_jpeg_encode(const uint8_t* in, uint8_t* out, int32_t* lengths, int32_t B, int32_t H, int32_t W, int32_t quality,
+                          int32_t subsampling, int32_t bgr, void* workspace, void* stream) {
+    API_BEGIN
+    const std::string w("ucdir_jpeg_encode");
+    require(quality >= 1 && quality <= 100, w + ": quality must lie in 1..100");
+    const char* bad = jpeg_encode_check(B, H, W, subsampling);
+    require(!bad, w + ": " + (bad ? bad : ""));
+    require((int64_t)B * H * W < (1LL << 31), w + ": more than 2^31 - 1 pixels");
+    require(in && out && lengths && workspace, w + ": null argument");
+    require(((uintptr_t)workspace & 15) == 0, w + ": workspace must be 16-byte aligned");
+    require(((uintptr_t)lengths & 3) == 0, w + ": lengths must be 4-byte aligned");
+    hipPointerAttribute_t pa;
+    HIPC(hipPointerGetAttributes(&pa, in));
+    require(pa.type == hipMemoryTypeDevice, w + ": in is not a device pointer");
+    const void* others[3] = {out, lengths, workspace};
+    const char* names[3] = {"out", "lengths", "workspace"};
+    for (int i = 0; i < 3; ++i) {
+        hipPointerAttribute_t po;
+        HIPC(hipPointerGetAttributes(&po, others[i]));
+        require(po.type == hipMemoryTypeDevice && po.device == pa.device, w + ": " + names[i] + " must live on the device of in");
+    }
+    const JpegEncLayout l = jpeg_encode_layout(B, H, W, subsampling);
+    const long long stride = ucdir_jpeg_encode_bound(H, W, subsampling);
+    JpegQuant qt;
+    jpeg_quant_tables(quality, qt.q);
+    JpegEncHeader header;                                  // a kernel argument of the scatter kernel: no copy, nothing to outlive
+    unsigned char hdr[sizeof(header.w)] = {0};
+    require(jpeg_enc::write_header(H, W, subsampling, qt.q, hdr) == jpeg_enc::HEADER_BYTES, w + ": header size");
+    std::memcpy(header.w, hdr, sizeof(hdr));
+    DevGuard dg(pa.device);
+    hipStream_t st = (hipStream_t)stream;
+    unsigned char* ws = (unsigned char*)workspace;
+    short* coef = (short*)(ws + l.coef);
+    unsigned int* boff = (unsigned int*)(ws + l.boff);
+    unsigned int* part = (unsigned int*)(ws + l.part);
+    unsigned int* totbits = (unsigned int*)(ws + l.totbits);
+    unsigned int* ffpart = (unsigned int*)(ws + l.ffpart);
+    unsigned int* raw = (unsigned int*)(ws + l.raw);
+    HIPC(hipMemsetAsync(raw, 0, (size_t)B * l.rawcap * 4, st));
+    const long long units = (l.nblk + 5) / 6;
+    const dim3 gblocks((unsigned)((units + 3) / 4), (unsigned)B), ggrp((unsigned)l.ngrp, (unsigned)B), gchunk((unsigned)l.nchunk, (unsigned)B);
+    if (subsampling == 0)
+        hipLaunchKernelGGL(jpeg_enc_blocks_kernel<0>, gblocks, dim3(256), 0, st, in, coef, H, W, (int)l.nblk, bgr ? 1 : 0, qt);
+    else
+        hipLaunchKernelGGL(jpeg_enc_blocks_kernel<2>, gblocks, dim3(256), 0, st, in, coef, H, W, (int)l.nblk, bgr ? 1 : 0, qt);
+    HIPC(hipGetLastError());
+    hipLaunchKernelGGL(jpeg_enc_len_kernel, ggrp, dim3(JPEG_ENC_GROUP), 0, st, (const short*)coef, (int)l.nblk, subsampling, boff, part);
+    HIPC(hipGetLastError());
+    hipLaunchKernelGGL(jpeg_enc_scan_bits_kernel, dim3((unsigned)B), dim3(256), 0, st, part, (int)l.ngrp, totbits);
+    HIPC(hipGetLastError());
+    hipLaunchKernelGGL(jpeg_enc_emit_kernel, ggrp, dim3(JPEG_ENC_GROUP), 0, st, (const short*)coef, (int)l.nblk, subsampling,
+                       (const unsigned int*)boff, (const unsigned int*)part, (const unsigned int*)totbits, raw, (long long)l.rawcap);
+    HIPC(hipGetLastError());
+    hipLaunchKernelGGL(jpeg_enc_count_kernel, gchunk, dim3(256), 0, st, (const unsigned int*)raw, (long long)l.rawcap,
+                       (const unsigned int*)totbits, ffpart);
+    HIPC(hipGetLastError());
+    hipLaunchKernelGGL(jpeg_enc_scan_ff_kernel, dim3((unsigned)B), dim3(256), 0, st, ffpart, (int)l.nchunk, (long long)l.rawcap,
+                       (const unsigned int*)totbits, stride, (int*)lengths);
+    HIPC(hipGetLastError());
+    hipLaunchKernelGGL(jpeg_enc_scatter_kernel, gchunk, dim3(256), 0, st, (const unsigned int*)raw, (long long)l.rawcap,
+                       (const unsigned int*)totbits, (const unsigned int*)ffpart, header, (const int*)lengths,
+                       (unsigned char*)out, stride);
     HIPC(hipGetLastError());
     API_END
 }

@@ -54,6 +54,11 @@ _SIGS = {
                                       c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ucdir_jpeg_roundtrip_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32]),
     "ucdir_jpeg_roundtrip": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "ucdir_jpeg_encode_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+    "ucdir_jpeg_encode_bound": (c_int64, [c_int32, c_int32, c_int32]),
+    "ucdir_jpeg_encode_header": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32]),
+    "ucdir_jpeg_encode": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
+                                    c_void_p]),
     "ucdir_resample_coeffs": (c_int32, [c_int32, c_int32, c_int32, c_void_p, c_void_p, POINTER(c_int32)]),
     "ucdir_resample_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32]),
     "ucdir_resample": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),

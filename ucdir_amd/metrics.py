@@ -20,6 +20,16 @@ def tensor2img_u8_device(tensor, min_max=(-1, 1)):
     return (t * 255.0).round().to(__import__("torch").uint8).permute(1, 2, 0).contiguous().cpu().numpy()
 
 
+def tensor2img_u8_batch_device(tensor, min_max=(-1, 1)):
+    """tensor2img_u8_device for a whole (B, 3, H, W) batch, left ON the device: the same clamp / rescale / round -> a contiguous
+    (B, H, W, 3) uint8 tensor, bit-equal per image to the per-image function (the operations are elementwise)."""
+    if tensor.dim() != 4 or tensor.shape[1] != 3:
+        raise ValueError(f"tensor2img_u8_batch_device takes a 4-D (B, 3, H, W) batch, got {tuple(tensor.shape)}")
+    t = tensor.detach().float().clamp(*min_max)
+    t = (t - min_max[0]) / (min_max[1] - min_max[0])
+    return (t * 255.0).round().to(__import__("torch").uint8).permute(0, 2, 3, 1).contiguous()
+
+
 def tensor2img(tensor, out_type=np.uint8, min_max=(-1, 1)):
     """core/metrics.py:8-34 for 3-D / single-image 4-D tensors: clamp, rescale to [0,1], HWC, round to uint8."""
     t = tensor.squeeze().float().cpu().clamp(*min_max)
@@ -136,6 +146,46 @@ def jpeg_roundtrip_device(x_u8, quality, bgr=True):
     out = torch.empty_like(x_u8)
     lib.check(L.ucdir_jpeg_roundtrip(_ptr(x), _ptr(out), B, H, W, int(quality), 1 if bgr else 0, _ptr(ws), _stream_ptr(x.device)))
     return out
+
+
+def jpeg_encode_device(x_u8, quality=100, subsampling=0, bgr=False):
+    """Baseline JPEG files of uint8 images, encoded on the GPU (csrc/jpeg_encode.hip.h): byte for byte what Pillow's
+    Image.save(JPEG, quality=quality, subsampling=subsampling) writes.  ``x_u8``: (B, H, W, 3) or (H, W, 3) contiguous uint8 CUDA
+    tensor, H and W from 1 -> a list of ``bytes``, one complete file per image, encoded on the current stream.  subsampling 0 is
+    4:4:4 (what save_jpg writes), 2 is 4:2:0 (libjpeg's default); bgr=True reads channel 0 as B and channel 2 as R.  The call waits
+    once, for the B file lengths; then only the used bytes of every slot cross PCIe, packed into one copy."""
+    import torch
+    from . import lib
+    from .ucdir import _ptr, _stream_ptr
+    if not torch.is_tensor(x_u8) or not x_u8.is_cuda:
+        raise ValueError("jpeg_encode_device takes a uint8 tensor on the GPU")
+    if x_u8.dtype != torch.uint8:
+        raise ValueError(f"jpeg_encode_device takes uint8 images, got {x_u8.dtype}")
+    if x_u8.dim() not in (3, 4) or x_u8.shape[-1] != 3 or x_u8.numel() == 0:
+        raise ValueError(f"jpeg_encode_device takes (B, H, W, 3) or (H, W, 3) images, got {tuple(x_u8.shape)}")
+    if not x_u8.is_contiguous():
+        raise ValueError("jpeg_encode_device takes a contiguous tensor")
+    if isinstance(quality, bool) or int(quality) != quality or not 1 <= quality <= 100:
+        raise ValueError(f"jpeg_encode_device: quality must be an integer in 1..100, got {quality!r}")
+    if isinstance(subsampling, bool) or subsampling not in (0, 2):
+        raise ValueError(f"jpeg_encode_device: subsampling must be 0 (4:4:4) or 2 (4:2:0), got {subsampling!r}")
+    x = x_u8 if x_u8.dim() == 4 else x_u8.unsqueeze(0)
+    B, H, W, _ = x.shape
+    L = lib.load()
+    nbytes, bound = L.ucdir_jpeg_encode_workspace_bytes(B, H, W, subsampling), L.ucdir_jpeg_encode_bound(H, W, subsampling)
+    if nbytes < 0 or bound < 0:
+        raise ValueError(f"jpeg_encode_device: {B} x {H} x {W} is outside what ucdir_jpeg_encode supports (include/ucdir_hip.h)")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    out = torch.empty((B, bound), dtype=torch.uint8, device=x.device)
+    lengths = torch.empty(B, dtype=torch.int32, device=x.device)
+    lib.check(L.ucdir_jpeg_encode(_ptr(x), _ptr(out), _ptr(lengths), B, H, W, int(quality), int(subsampling), 1 if bgr else 0, _ptr(ws),
+                                  _stream_ptr(x.device)))
+    n = lengths.cpu().tolist()                      # the synchronisation
+    if min(n) < 0:
+        raise lib.UcdirError("ucdir_jpeg_encode: a file would pass ucdir_jpeg_encode_bound; nothing was written for it")
+    packed = torch.cat([out[i, :n[i]] for i in range(B)]).cpu().numpy().tobytes()
+    ends = np.cumsum(n).tolist()
+    return [packed[e - k:e] for e, k in zip(ends, n)]
 
 
 RESAMPLE_FILTERS = {"box": 0, "bilinear": 1, "bicubic": 2, "lanczos": 3}

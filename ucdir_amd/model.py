@@ -109,6 +109,28 @@ class DDPM:
         out["INF"] = cv(pre[j, :, 64:-64, 64:-64]) if pre is not None else cv(self.data["SR"][j])
         return out
 
+    def visuals_jpeg(self, quality=100, subsampling=0):
+        """The files save_jpg would write for the images of the last ``test()``, encoded ON THE DEVICE (metrics.jpeg_encode_device):
+        a list with one dict per image, ``SR`` / ``HR`` / ``LR`` / ``INF`` -> bytes.  Built from the tensors and slices of
+        ``visuals_u8``; kinds of one (H, W) are encoded together, so equal-sized SR / HR / LR / INF take one call for the batch."""
+        from .metrics import jpeg_encode_device, tensor2img_u8_batch_device
+        B = self.data["SR"].shape[0]
+        sr = self.SR[self.SR.shape[0] - B:] if self.SR.dim() == 4 else self.SR.unsqueeze(0)
+        pre = getattr(self.netG, "pre_initx", None)
+        kinds = OrderedDict(SR=sr, HR=self.data["HR"], LR=self.data["LR"] if "LR" in self.data else self.data["SR"],
+                            INF=pre[:, :, 64:-64, 64:-64] if pre is not None else self.data["SR"])
+        by_shape = OrderedDict()
+        for name, t in kinds.items():
+            by_shape.setdefault(tuple(t.shape[-2:]), []).append(name)
+        out = [OrderedDict() for _ in range(B)]
+        for names in by_shape.values():
+            u8 = torch.cat([tensor2img_u8_batch_device(kinds[k]) for k in names])
+            files = jpeg_encode_device(u8, quality=quality, subsampling=subsampling)
+            for i, k in enumerate(names):
+                for j in range(B):
+                    out[j][k] = files[i * B + j]
+        return out
+
     def current_metrics(self):
         """(psnr list, ssim list) of the images of the last ``test()``: the final SR block against data["HR"], scored on the GPU
         (metrics.psnr_ssim_device) with the same uint8 quantisation as ``visuals_u8``; one device-to-host copy."""
