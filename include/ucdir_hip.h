@@ -240,6 +240,26 @@ int32_t ucdir_niqe_features(const float* x, int64_t x_sn, int64_t x_sc, int64_t 
                             const double* window49, const double* tables, double* feats,
                             float* mscn_or_null, void* workspace, void* stream);
 
+/* Degradation operators of the real-world SR val task (additive in ABI 5; csrc/realsr.hip.h; reference data/degradations.py:13-89
+ * filter2D / USMSharp, data/diffjpeg.py DiffJPEG(differentiable=False)).  All tensors fp32 NCHW contiguous on one device; no
+ * allocation, no synchronisation; x and y must not alias.
+ * ucdir_filter2d: y = correlation (no flip) of the reflect-padded x (pad k / 2, the edge not repeated: PyTorch's `reflect`) with a
+ *   k x k kernel; x, y (B, C, H, W); kernels (B, k, k) with per_sample != 0 (sample b uses kernels[b] on all its channels), else
+ *   (1, k, k).  k odd, 1..21; H and W above k / 2 (the pad PyTorch accepts); B * C at most 65535.
+ * ucdir_usm_sharp: USMSharp(radius).forward(x, weight, threshold): K = fp32(g g^T), g = cv2.getGaussianKernel(radius | 1, 0) in
+ *   float64 (k at most 21); blur = filter2d(x, K); res = x - blur; mask = |res| * 255 > threshold; soft = filter2d(mask, K);
+ *   y = soft * clip(x + weight * res, 0, 1) + (1 - soft) * x.  workspace: device buffer of ucdir_usm_sharp_workspace_bytes(B, C, H,
+ *   W) bytes (-1 on a bad shape): the mask plane.
+ * ucdir_diffjpeg: x, y (B, 3, H, W) RGB in [0, 1]; factors: B fp32 ON THE DEVICE, the compression factor of every sample
+ *   (quality_to_factor of its quality).  Zero-pad to multiples of 16, * 255, YCbCr, 2 x 2 chroma means, 8 x 8 DCT, divide by
+ *   fp32(table * factor) in IEEE arithmetic, round half to even, and all the way back; clamp, / 255, crop.  x == y is allowed. */
+int32_t ucdir_filter2d(const float* x, const float* kernels, float* y, int32_t B, int32_t C, int32_t H, int32_t W,
+                       int32_t k, int32_t per_sample, void* stream);
+int64_t ucdir_usm_sharp_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W);
+int32_t ucdir_usm_sharp(const float* x, float* y, int32_t B, int32_t C, int32_t H, int32_t W, int32_t radius,
+                        float weight, float threshold, void* workspace, void* stream);
+int32_t ucdir_diffjpeg(const float* x, float* y, const float* factors, int32_t B, int32_t H, int32_t W, void* stream);
+
 /* ---- introspection (tests / profiling) ---------------------------------------------------
  * Copy the activation a layer produced in the last forward into dst as (B,C,Hc,Wc) fp32 NCHW
  * (Hc, Wc = compute size).  layer = state_dict prefix ("downs.0", "ups.7", "mid.0", ...),

@@ -30,9 +30,15 @@ sys.path.insert(0, ROOT)
 from ucdir_amd import config as Config  # noqa: E402
 from ucdir_amd import metrics as Metrics  # noqa: E402
 from ucdir_amd import model as Model  # noqa: E402
-from ucdir_amd.data import ImagenetJPGDataset, ImagenetSRDataset, PairDataset  # noqa: E402
+from ucdir_amd.data import ImagenetJPGDataset, ImagenetSRDataset, PairDataset, RealESRGANDataset  # noqa: E402
 
-VAL_DATASETS = {"PairDataset": PairDataset, "ImagenetJPGDataset": ImagenetJPGDataset, "ImagenetSRDataset": ImagenetSRDataset}
+VAL_DATASETS = {"PairDataset": PairDataset, "ImagenetJPGDataset": ImagenetJPGDataset, "ImagenetSRDataset": ImagenetSRDataset,
+                "RealESRGANDataset": RealESRGANDataset}
+
+
+def item_hw(item):
+    """(H, W) of the image a val item is restored at: its SR, or the gt of a gt / lq item (DDPM_realsr scales lq up to it)."""
+    return tuple((item["SR"] if "SR" in item else item["gt"]).shape[-2:])
 
 
 def make_val_dataset(val_opt):
@@ -161,9 +167,10 @@ def main(argv=None):
         is written for a batch; the reference's val loader feeds it batch_size 1, data/__init__.py:47)."""
         nonlocal tot_psnr, tot_ssim, tot_niqe, n, t_restore, n_restored
         items = [g[1] for g in group]
-        data = {k: torch.stack([it[k] for it in items]) for k in ("HR", "SR", "LR") if k in items[0]}
+        data = {k: torch.stack([it[k] for it in items]) for k in ("HR", "SR", "LR", "gt", "lq") if k in items[0]}
         data["Index"] = [g[0] for g in group]                    # DDPM.test derives every image's noise stream from its index
-        small = (items[0]["SR"].shape[-2] + 128) * (items[0]["SR"].shape[-1] + 128) <= thr
+        h, w = item_hw(items[0])
+        small = (h + 128) * (w + 128) <= thr
         dn.set_graph(len(group) == 1 and small)                  # batch-1 remainders: HIP-graph replay of the forward (latency path)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -210,7 +217,7 @@ def main(argv=None):
     nsmall = 0
     for i in idxs:
         item = val_set[i]
-        h, w = item["SR"].shape[-2:]
+        h, w = item_hw(item)
         shared = world > 1 and (h + 128) * (w + 128) > thr        # DDPM.test pads 64 per side: this image is patch-split
         if not shared:
             mine = (nsmall % world) == rank

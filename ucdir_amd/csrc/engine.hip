@@ -35,6 +35,7 @@
 #include "jpeg_encode.hip.h"
 #include "resample.hip.h"
 #include "niqe.hip.h"
+#include "realsr.hip.h"
 #include "pack.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -2165,6 +2166,130 @@ int32_t ucdir_niqe_features(const float* x, int64_t x_sn, int64_t x_sc, int64_t 
                            tables, feats);
         HIPC(hipGetLastError());
     }
+    API_END
+}
+
+// Degradation operators of the real-world SR val task (csrc/realsr.hip.h).
+static int realsr_same_device(const std::string& w, const void* first, const char* first_name, const void* const* others,
+                              const char* const* names, int n) {
+    hipPointerAttribute_t pa;
+    HIPC(hipPointerGetAttributes(&pa, first));
+    require(pa.type == hipMemoryTypeDevice, w + ": " + first_name + " is not a device pointer");
+    for (int i = 0; i < n; ++i) {
+        hipPointerAttribute_t po;
+        HIPC(hipPointerGetAttributes(&po, others[i]));
+        require(po.type == hipMemoryTypeDevice && po.device == pa.device, w + ": " + names[i] + " must live on the device of " + first_name);
+    }
+    return pa.device;
+}
+
+static void filter2d_check(const std::string& w, int32_t B, int32_t C, int32_t H, int32_t W, int32_t k) {
+    require(B > 0 && C > 0 && H > 0 && W > 0, w + ": bad shape (B, C, H and W at least 1)");
+    require((int64_t)B * C <= 65535, w + ": more than 65535 planes (B * C)");
+    require(k >= 1 && (k & 1) == 1, w + ": the kernel size must be odd");
+    require(k <= F2D_KMAX, w + ": the kernel size must be at most 21");
+    require(H > k / 2 && W > k / 2, w + ": the reflect pad k / 2 must be smaller than H and W");
+    require((int64_t)((H + F2D_TH - 1) / F2D_TH) * ((W + F2D_TW - 1) / F2D_TW) < (1LL << 31), w + ": image too large");
+}
+
+int32_t ucdir_filter2d(const float* x, const float* kernels, float* y, int32_t B, int32_t C, int32_t H, int32_t W, int32_t k,
+                       int32_t per_sample, void* stream) {
+    API_BEGIN
+    const std::string w("ucdir_filter2d");
+    filter2d_check(w, B, C, H, W, k);
+    require(x && kernels && y, w + ": null argument");
+    require(x != y, w + ": x and y must not alias");
+    const void* others[2] = {kernels, y};
+    const char* names[2] = {"kernels", "y"};
+    DevGuard dg(realsr_same_device(w, x, "x", others, names, 2));
+    const unsigned tiles = (unsigned)(((H + F2D_TH - 1) / F2D_TH) * ((W + F2D_TW - 1) / F2D_TW));
+    hipLaunchKernelGGL(filter2d_kernel<0>, dim3(tiles, (unsigned)(B * C)), dim3(256), 0, (hipStream_t)stream, x,
+                       (const unsigned char*)nullptr, kernels, UsmGauss{}, y, (unsigned char*)nullptr, C, H, W, k, per_sample ? 1 : 0,
+                       0.f, 0.f);
+    HIPC(hipGetLastError());
+    API_END
+}
+
+// cv2.getGaussianKernel(k, sigma = 0) in float64: the fixed tables OpenCV keeps for k <= 7, else sigma = 0.3 ((k - 1) / 2 - 1) + 0.8
+static void usm_gauss(int k, double* g) {
+    static const double small[4][7] = {{1.0}, {0.25, 0.5, 0.25}, {0.0625, 0.25, 0.375, 0.25, 0.0625},
+                                       {0.03125, 0.109375, 0.21875, 0.28125, 0.21875, 0.109375, 0.03125}};
+    if (k <= 7) {
+        for (int i = 0; i < k; ++i) g[i] = small[k >> 1][i];
+        return;
+    }
+    const double sigma = 0.3 * ((k - 1) * 0.5 - 1.0) + 0.8, s2 = -0.5 / (sigma * sigma);
+    double sum = 0.0;
+    for (int i = 0; i < k; ++i) {
+        const double d = i - (k - 1) * 0.5;
+        g[i] = std::exp(s2 * d * d);
+        sum += g[i];
+    }
+    for (int i = 0; i < k; ++i) g[i] *= 1.0 / sum;
+}
+
+int64_t ucdir_usm_sharp_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W) {
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return -1;
+    return (int64_t)B * C * H * W;                        // the mask, one byte per element
+}
+
+int32_t ucdir_usm_sharp(const float* x, float* y, int32_t B, int32_t C, int32_t H, int32_t W, int32_t radius, float weight,
+                        float threshold, void* workspace, void* stream) {
+    API_BEGIN
+    const std::string w("ucdir_usm_sharp");
+    require(radius >= 1, w + ": radius must be at least 1");
+    const int k = radius | 1;                            // an even radius takes the next odd size, as the reference
+    filter2d_check(w, B, C, H, W, k);
+    require(x && y && workspace, w + ": null argument");
+    require(x != y, w + ": x and y must not alias");
+    const void* others[2] = {y, workspace};
+    const char* names[2] = {"y", "workspace"};
+    DevGuard dg(realsr_same_device(w, x, "x", others, names, 2));
+    UsmGauss gs{};
+    usm_gauss(k, gs.g);
+    const dim3 grid((unsigned)(((H + F2D_TH - 1) / F2D_TH) * ((W + F2D_TW - 1) / F2D_TW)), (unsigned)(B * C));
+    unsigned char* mask = (unsigned char*)workspace;
+    hipLaunchKernelGGL(filter2d_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, x, (const unsigned char*)nullptr,
+                       (const float*)nullptr, gs, y, mask, C, H, W, k, 0, weight, threshold);
+    HIPC(hipGetLastError());
+    hipLaunchKernelGGL(filter2d_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, x, (const unsigned char*)mask,
+                       (const float*)nullptr, gs, y, (unsigned char*)nullptr, C, H, W, k, 0, weight, threshold);
+    HIPC(hipGetLastError());
+    API_END
+}
+
+int32_t ucdir_diffjpeg(const float* x, float* y, const float* factors, int32_t B, int32_t H, int32_t W, void* stream) {
+    API_BEGIN
+    const std::string w("ucdir_diffjpeg");
+    require(B > 0 && B <= 65535 && H > 0 && W > 0, w + ": bad shape (B in 1..65535, H and W at least 1)");
+    require((int64_t)((H + 15) / 16) * ((W + 15) / 16) < (1LL << 31), w + ": image too large");
+    require(x && y && factors, w + ": null argument");
+    const void* others[2] = {y, factors};
+    const char* names[2] = {"y", "factors"};
+    DevGuard dg(realsr_same_device(w, x, "x", others, names, 2));
+    static const float luma[64] = {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56,
+                                   14, 17, 22, 29, 51, 87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92,
+                                   49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
+    static const float chroma4[16] = {17, 18, 24, 47, 18, 21, 26, 66, 24, 26, 56, 99, 47, 66, 99, 99};
+    DiffJpegTables t;
+    const double pi = 3.14159265358979323846;
+    for (int i = 0; i < 8; ++i)
+        for (int u = 0; u < 8; ++u) t.cosv[i][u] = std::cos((2 * i + 1) * u * pi / 16);
+    for (int u = 0; u < 8; ++u)
+        for (int v = 0; v < 8; ++v) {
+            const double au = u ? 1.0 : 1.0 / std::sqrt(2.0), av = v ? 1.0 : 1.0 / std::sqrt(2.0);
+            t.table[0][u * 8 + v] = luma[v * 8 + u];     // the reference transposes the luma table
+            t.table[1][u * 8 + v] = (u < 4 && v < 4) ? chroma4[v * 4 + u] : 99.f;
+            t.scale[u * 8 + v] = (float)(au * av * 0.25);
+            t.alpha[u * 8 + v] = (float)(au * av);
+        }
+    const float fwd[3][3] = {{0.299f, 0.587f, 0.114f}, {-0.168736f, -0.331264f, 0.5f}, {0.5f, -0.418688f, -0.081312f}};
+    const float inv[3][3] = {{1.f, 0.f, 1.402f}, {1.f, -0.344136f, -0.714136f}, {1.f, 1.772f, 0.f}};
+    std::memcpy(t.fwd, fwd, sizeof fwd);
+    std::memcpy(t.inv, inv, sizeof inv);
+    hipLaunchKernelGGL(diffjpeg_kernel, dim3((unsigned)(((H + 15) / 16) * ((W + 15) / 16)), (unsigned)B), dim3(256), 0,
+                       (hipStream_t)stream, x, y, factors, H, W, t);
+    HIPC(hipGetLastError());
     API_END
 }
 

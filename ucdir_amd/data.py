@@ -1,7 +1,8 @@
 """Paired-image loader for ``-p val`` (reference: data/LRHR_dataset.py:230-297 PairDataset, val split, datatype img):
 sorted file lists of dataroot.lq / dataroot.gt, RGB, scaled to [-1, 1] (data/util.py:76-83), dict with 'HR', 'SR', 'LR',
 'Index'; the JPEG-restoration loader ImagenetJPGDataset (reference: data/LRHR_dataset.py:446-516); and the 4x super-resolution
-loader ImagenetSRDataset (reference: data/LRHR_dataset.py:385-443)."""
+loader ImagenetSRDataset (reference: data/LRHR_dataset.py:385-443); and the real-world SR loader RealESRGANDataset (reference:
+data/LRHR_dataset.py:668-807)."""
 import os
 
 import numpy as np
@@ -165,3 +166,67 @@ class ImagenetSRDataset:
         hr_u8, self.last_lr64, sr_u8 = self.degrade_u8(img)
         sr = _u8_to_unit(sr_u8)
         return {"HR": _u8_to_unit(hr_u8), "SR": sr, "LR": sr, "Index": i}
+
+
+def reflect101_pad(img, size):
+    """Pad an (H, W, 3) array bottom and right up to ``size`` like cv2.copyMakeBorder(..., BORDER_REFLECT_101): the mirror does not
+    repeat the edge and starts over when the image is shorter than the pad."""
+    def idx(n):
+        if n >= size:
+            return np.arange(n)
+        if n == 1:
+            return np.zeros(size, dtype=np.int64)
+        i = np.arange(size) % (2 * n - 2)
+        return np.where(i < n, i, 2 * n - 2 - i)
+    return img[idx(img.shape[0])][:, idx(img.shape[1])]
+
+
+class RealESRGANDataset:
+    """Real-world SR val loader (reference: data/LRHR_dataset.py:668-807, RealESRGANDataset): file names from the first field of each
+    line of dataroot.txt under dataroot.root.  ``gt`` = the centred ``crop_size`` crop of the RGB image in [0, 1] (smaller images
+    are padded bottom and right first), decoded on the host and uploaded once; ``lq`` = gt after the second-order degradation
+    (degradations.realsr_degrade_device) at crop_size / scale, computed on the current GPU.
+
+    The reference's val split returns no ``lq`` and draws from global generators; here every random decision of image ``i`` comes
+    from a stream seeded by ``i`` (degradations.draw_realsr_params), so an image's input does not depend on rank, batch or
+    order.  ``data_args.dopt`` / ``data_args.param``: the degradation and kernel settings, a name from
+    config/realsr_degradations.yaml or a dict."""
+
+    def __init__(self, data_args, phase="val"):
+        from .degradations import load_settings
+        root = data_args["dataroot"]
+        if "root" not in root or "txt" not in root:
+            raise ValueError("RealESRGANDataset reads dataroot.root and dataroot.txt (an image directory and a list of names), got "
+                             "dataroot keys %s" % sorted(root))
+        self.root = root["root"]
+        with open(root["txt"]) as f:
+            names = [ln.split()[0] for ln in f if ln.strip()]
+        n = data_args.get("data_len", -1)
+        if n and n > 0:
+            names = names[:n]
+        self.hr_path = [os.path.join(self.root, s) for s in names]
+        self.sr_path = self.hr_path                  # sr.py names its outputs after sr_path
+        self.crop_size = int(data_args.get("crop_size") or 256)
+        if self.crop_size < 32 or self.crop_size % 4:
+            raise ValueError("RealESRGANDataset: crop_size must be a multiple of 4 and at least 32, got %d" % self.crop_size)
+        self.dopt = load_settings(data_args.get("dopt") or "dopt")
+        self.kopt = load_settings(data_args.get("param") or "param")
+
+    def __len__(self):
+        return len(self.hr_path)
+
+    def load_u8(self, i):
+        """Host half: decode to RGB, pad to crop_size, centred crop -> (crop_size, crop_size, 3) uint8, contiguous."""
+        from PIL import Image
+        img = reflect101_pad(np.asarray(Image.open(self.hr_path[i]).convert("RGB"), dtype=np.uint8), self.crop_size)
+        cs = self.crop_size
+        top, left = (img.shape[0] - cs) // 2, (img.shape[1] - cs) // 2
+        return np.ascontiguousarray(img[top:top + cs, left:left + cs])
+
+    def __getitem__(self, i):
+        from .degradations import draw_realsr_params, realsr_degrade_device
+        dev = torch.device("cuda", torch.cuda.current_device())
+        # u8 / 255 in numpy float32 on the host, as the reference forms it (a division by a scalar on the GPU can land one ulp away)
+        gt = torch.from_numpy(np.ascontiguousarray((self.load_u8(i).astype(np.float32) / 255.0).transpose(2, 0, 1))).to(dev)
+        lq = realsr_degrade_device(gt.unsqueeze(0), draw_realsr_params(i, self.dopt, self.kopt), self.dopt)[0]
+        return {"gt": gt, "lq": lq, "Index": i}

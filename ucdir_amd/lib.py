@@ -65,6 +65,10 @@ _SIGS = {
     "ucdir_niqe_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "ucdir_niqe_features": (c_int32, [c_void_p, c_int64, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ucdir_filter2d": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "ucdir_usm_sharp_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+    "ucdir_usm_sharp": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_void_p, c_void_p]),
+    "ucdir_diffjpeg": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "ucdir_sampler_step": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float,
                                      c_float, c_void_p]),
     "ucdir_debug_read": (c_int32, [c_void_p, c_char_p, c_char_p, c_void_p, c_int64, c_void_p]),

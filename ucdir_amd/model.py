@@ -203,7 +203,68 @@ def load_checkpoint_state(netG, sd, strict=False):
             "missing_non_network": list(res.missing_keys)}
 
 
+def _indices(idx, n):
+    """data['Index'] as a list of ``n`` ints (a tensor, a list or one number; absent: 0, 1, ...)."""
+    if idx is None:
+        return list(range(n))
+    if torch.is_tensor(idx):
+        return [int(v) for v in idx.reshape(-1).tolist()]
+    if isinstance(idx, (list, tuple)):
+        return [int(v) for v in idx]
+    return [int(idx)]
+
+
+class DDPM_bnoise(DDPM):
+    """``DDPM`` whose input carries extra Gaussian noise (reference model/model.py:270-280): SR += 2 * 50 / 255 * N(0, 1).  Image
+    ``i`` draws the Philox stream of its own seed (``image_seed_base + 1000003 i``, the seed ``test()`` gives its sampler; base 0
+    when none is set) at step 0xFFFFFFFF, which no sampler step reaches, so its noise does not depend on batch or rank."""
+    NOISE_STEP = 0xFFFFFFFF
+    NOISE_SCALE = 2 * 50.0 / 255.0
+
+    def feed_data(self, data):
+        from .ucdir import fill_normal_
+        super().feed_data(data)
+        sr = self.data["SR"]
+        B, per = sr.shape[0], sr[0].numel()
+        idxs = _indices(self.data.get("Index"), B)
+        if len(idxs) != B:
+            raise ValueError("data['Index'] must hold one index per image of the batch")
+        base = int(getattr(self, "image_seed_base", None) or 0)
+        seeds = torch.tensor([(base + 1000003 * i + 2 ** 63) % 2 ** 64 - 2 ** 63 for i in idxs], dtype=torch.int64, device=sr.device)
+        buf = torch.empty((B, (per + 3) // 4 * 4), dtype=torch.float32, device=sr.device)      # per-sample streams come in fours
+        fill_normal_(buf, 0, self.NOISE_STEP, seeds=seeds)
+        self.data["SR"] = sr + buf[:, :per].reshape(sr.shape) * self.NOISE_SCALE
+
+
+class DDPM_realsr(DDPM):
+    """``DDPM`` of the real-world SR task (reference model/model.py:395-577, the non-training branch of feed_data, with the scale-up
+    of the synthesis branch added): the loader hands over ``gt`` and the degraded ``lq`` in [0, 1] (RealESRGANDataset);
+    SR = LR = lq scaled up bilinearly by dopt.scale, HR = the USM-sharpened gt (``gt_usm``, default true) or gt, all * 2 - 1."""
+
+    def __init__(self, opt, device=None):
+        super().__init__(opt, device)
+        from .degradations import load_settings
+        self.dopt = load_settings(opt["dopt"] or "dopt")
+
+    def feed_data(self, data):
+        from .degradations import usm_sharp_device
+        lq = data["lq"].to(self.device, torch.float32)
+        gt = data["gt"].to(self.device, torch.float32).contiguous()
+        sr = F.interpolate(lq, scale_factor=self.dopt["scale"], mode="bilinear") * 2.0 - 1.0
+        hr = usm_sharp_device(gt) if self.opt.get("gt_usm", True) else gt
+        self.data = {"SR": sr, "LR": sr, "HR": hr * 2.0 - 1.0}
+        if "Index" in data:
+            self.data["Index"] = data["Index"]
+
+
+MODELS = {"DDPM": DDPM, "DDPM_bnoise": DDPM_bnoise, "DDPM_realsr": DDPM_realsr}
+
+
 def create_model(opt, device=None):
-    m = DDPM(opt, device)
+    """The model class named by ``model.name`` (reference model/__init__.py:5-10; absent: DDPM)."""
+    name = opt["model"].get("name") or "DDPM"
+    if name not in MODELS:
+        raise ValueError("model.name %r is not supported (known: %s)" % (name, ", ".join(MODELS)))
+    m = MODELS[name](opt, device)
     logger.info("Model [{:s}] is created.".format(m.__class__.__name__))
     return m
