@@ -320,6 +320,31 @@ int32_t ucdir_predictor_forward(ucdir_predictor* p, const float* x, float* y, in
  * half is zero.  Unknown names and a wrong dst_elems are errors. */
 int32_t ucdir_predictor_debug_read(ucdir_predictor* p, const char* name, float* dst, int64_t dst_elems, void* stream);
 
+/* ---- LPIPS (AlexNet variant) of the val loop (additive in ABI 5; csrc/lpips.hip.h): for B pairs of uint8 RGB images,
+ *   x = q / 127.5 - 1, (x - shift) / scale per channel, the five ReLU taps of torchvision's AlexNet `features`, per tap
+ *   d_l = mean_{h,w} sum_c lin_l[c] (n(f0) - n(f1))^2 with n(f) = f / (sqrt(sum_c f^2) + 1e-10), LPIPS = sum_l d_l.
+ * All convolutions run in exact fp32 (v_mfma_f32_32x32x2_f32), the distances in float64.
+ *   create            stores the ordinal only; no device call is made before finalize;
+ *   load_weight       name = "features.{0,3,6,8,10}.{weight,bias}" (torchvision's AlexNet state dict) or "lin{0..4}.model.1.weight"
+ *                     (the lpips package's alex.pth; shape (1, C, 1, 1) or (C)); data_host fp32 in the reference shape.  Unknown
+ *                     names and wrong shapes are errors;
+ *   finalize          packs the conv weights K-major and uploads; an error names the first of the 15 tensors that is missing;
+ *   workspace_bytes   size of the caller's device workspace (16-byte aligned); -1 on a refused shape: H and W at least 31;
+ *   forward           a_u8, b_u8: (B, H, W, 3) uint8, HWC, contiguous; scores_f64: (B) and per_layer_f64: (B, 5) float64, all ON THE
+ *                     OBJECT'S DEVICE.  Asynchronous on `stream`, no allocation, no atomics: pair j's score has the same bits in
+ *                     every batch and on every call;
+ *   debug_read        the ReLU features of tap `layer` (0..4) of the last forward's first (which = 0) or second (1) input as
+ *                     (B, C, H_l, W_l) fp32 NCHW (tests).  They live in that forward's workspace, which must still be alive. */
+typedef struct ucdir_lpips ucdir_lpips;
+int32_t ucdir_lpips_create(int32_t device, ucdir_lpips** out);
+void    ucdir_lpips_destroy(ucdir_lpips* p);
+int32_t ucdir_lpips_load_weight(ucdir_lpips* p, const char* name, const float* data_host, const int64_t* shape, int32_t ndim);
+int32_t ucdir_lpips_finalize(ucdir_lpips* p);
+int64_t ucdir_lpips_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int32_t ucdir_lpips_forward(ucdir_lpips* p, const uint8_t* a_u8, const uint8_t* b_u8, int32_t B, int32_t H, int32_t W,
+                            double* scores_f64, double* per_layer_f64, void* workspace, void* stream);
+int32_t ucdir_lpips_debug_read(ucdir_lpips* p, int32_t layer, int32_t which, float* dst, int64_t dst_elems, void* stream);
+
 /* ---- single-operator entry points (unit parity tests; fp32 NCHW in/out, bf16 inside) -----
  * conv: y = act(conv(GN?(cat[x0,x1]))) with 3x3 (mode 0 stride 1, 1 stride-2 down,
  * 2 nearest-x2-up then 3x3) or 1x1 (ksize 1).  gamma/beta NULL = no GroupNorm fold. */

@@ -3,7 +3,7 @@
 
 Counterpart of the reference's ``sr.py`` val branch (sr.py:320-400, 505-586): same flags, same YAML
 schema, same per-image outputs ``{results}/{fname}_{name}_{sr,hr,lr,inf}.jpg`` and the
-``# Validation # PSNR/SSIM`` log lines; ``--niqe`` adds the no-reference score of the reference's ``eval1.py``.  One process per GPU; with N ranks
+``# Validation # PSNR/SSIM`` log lines; ``--niqe`` adds the no-reference score of the reference's ``eval1.py``, ``--lpips`` its LPIPS.  One process per GPU; with N ranks
 (``python -m torch.distributed.run --nproc-per-node N sr.py ...``):
   * images small enough for one denoiser call are strided over ranks like the reference's EnlargedSampler
     (data/data_sampler.py:44-45), no data-path collective;
@@ -108,6 +108,11 @@ def make_parser():
                         help="also score the restored images with NIQE, the no-reference score of the reference's eval1.py")
     parser.add_argument("--niqe-params", type=str, default="./metric/niqe_pris_params.npz",
                         help="pristine-model statistics of NIQE (the reference's metric/niqe_pris_params.npz)")
+    parser.add_argument("--lpips", action="store_true",
+                        help="also score the restored images against HR with LPIPS (AlexNet variant), the perceptual score of the "
+                             "reference's eval1.py")
+    parser.add_argument("--lpips-weights", type=str, nargs="+", default=[], metavar="FILE",
+                        help="LPIPS weights: torchvision's AlexNet state dict and the lpips package's alex.pth (.pth or .npz), merged")
     return parser
 
 
@@ -115,6 +120,8 @@ def main(argv=None):
     args = make_parser().parse_args(argv)
     if args.phase != "val":
         raise SystemExit("only -p val is implemented (sampling path); training is out of scope of this build")
+    # a missing LPIPS weight file or tensor stops the run here, before a device is touched or the model is built
+    lpips_weights = Metrics.load_lpips_weights(args.lpips_weights) if args.lpips else None
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -139,6 +146,7 @@ def main(argv=None):
         opt["path"]["resume_state"] = None
     diffusion = Model.create_model(opt)
     diffusion.niqe_params = niqe_params
+    diffusion.lpips_weights = lpips_weights
     if args.synthetic_weights:
         from ucdir_amd.weights import synth_state_dict
         sd = synth_state_dict(diffusion.netG.denoise_fn.cfg, 0)
@@ -148,7 +156,7 @@ def main(argv=None):
     logger.info("Begin Model Evaluation. len %d" % len(val_set))
     result_path = opt["path"]["results"]
     os.makedirs(result_path, exist_ok=True)
-    tot_psnr = tot_ssim = tot_niqe = 0.0
+    tot_psnr = tot_ssim = tot_niqe = tot_lpips = 0.0
     n = 0
     idxs = list(range(len(val_set)))
     if args.max_images > 0:
@@ -165,7 +173,7 @@ def main(argv=None):
     def restore(group):
         """One DDPM.test call for a group of images of identical (H, W): a batch is B independent restorations (model/diffusion.py:185-211
         is written for a batch; the reference's val loader feeds it batch_size 1, data/__init__.py:47)."""
-        nonlocal tot_psnr, tot_ssim, tot_niqe, n, t_restore, n_restored
+        nonlocal tot_psnr, tot_ssim, tot_niqe, tot_lpips, n, t_restore, n_restored
         items = [g[1] for g in group]
         data = {k: torch.stack([it[k] for it in items]) for k in ("HR", "SR", "LR", "gt", "lq") if k in items[0]}
         data["Index"] = [g[0] for g in group]                    # DDPM.test derives every image's noise stream from its index
@@ -187,7 +195,8 @@ def main(argv=None):
         dev_scores = diffusion.current_metrics() if args.metrics_device == "gpu" else None
         dev_niqe = diffusion.current_niqe() if args.niqe and args.metrics_device == "gpu" else None
         jpgs = diffusion.visuals_jpeg() if args.jpeg_device == "gpu" else None      # the four files of every image, as bytes
-        need_u8 = jpgs is None or dev_scores is None or (args.niqe and dev_niqe is None)
+        dev_lpips = diffusion.current_lpips() if args.lpips and args.metrics_device == "gpu" else None
+        need_u8 = jpgs is None or dev_scores is None or (args.niqe and dev_niqe is None) or (args.lpips and dev_lpips is None)
         for j, (i, _, _) in enumerate(group):
             fname = os.path.splitext(os.path.basename(val_set.sr_path[i]))[0]
             if need_u8:                                           # the uint8 images cross PCIe for Pillow or for host scoring only
@@ -210,6 +219,8 @@ def main(argv=None):
                 tot_ssim += Metrics.calculate_ssim(sr_img, hr_img)
             if args.niqe:                                         # the uint8 SR image itself, not the JPEG read back
                 tot_niqe += dev_niqe[j] if dev_niqe is not None else Metrics.calculate_niqe(sr_img, niqe_params)
+            if args.lpips:
+                tot_lpips += dev_lpips[j] if dev_lpips is not None else Metrics.calculate_lpips(sr_img, hr_img, lpips_weights)
             n += 1
             logger.info("val index %d" % i)
 
@@ -238,18 +249,22 @@ def main(argv=None):
         logger.info("restored %d images in %.2f s on this rank (%.2f img/s, batches of up to %d)" % (n_restored, t_restore, n_restored / t_restore, args.batch))
     main.last_throughput = (n_restored, t_restore)
     main.last_groups = group_times
-    acc = torch.tensor([tot_psnr, tot_ssim, float(n), tot_niqe], dtype=torch.float64, device="cuda")
+    acc = torch.tensor([tot_psnr, tot_ssim, float(n), tot_niqe, tot_lpips], dtype=torch.float64, device="cuda")
     if world > 1:
         dist.all_reduce(acc)
     avg_psnr, avg_ssim = (acc[0] / acc[2]).item(), (acc[1] / acc[2]).item()
     logger.info("# Validation # PSNR: {:.4e}".format(avg_psnr))
     logger.info("# Validation # SSIM: {:.4e}".format(avg_ssim))
     main.last_niqe = (acc[3] / acc[2]).item() if args.niqe else None
+    main.last_lpips = (acc[4] / acc[2]).item() if args.lpips else None
+    line = "psnr: {:.4e}, ssim: {:.4e}".format(avg_psnr, avg_ssim)
     if args.niqe:
         logger.info("# Validation # NIQE: {:.4e}".format(main.last_niqe))
-        logging.getLogger("val").info("psnr: {:.4e}, ssim: {:.4e}, niqe: {:.4e}".format(avg_psnr, avg_ssim, main.last_niqe))
-    else:
-        logging.getLogger("val").info("psnr: {:.4e}, ssim: {:.4e}".format(avg_psnr, avg_ssim))
+        line += ", niqe: {:.4e}".format(main.last_niqe)
+    if args.lpips:
+        logger.info("# Validation # LPIPS: {:.4e}".format(main.last_lpips))
+        line += ", lpips: {:.4e}".format(main.last_lpips)
+    logging.getLogger("val").info(line)
     if world > 1:
         dist.destroy_process_group()
     return avg_psnr, avg_ssim

@@ -86,6 +86,13 @@ _SIGS = {
     "ucdir_predictor_finalize": (c_int32, [c_void_p]),
     "ucdir_predictor_forward": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "ucdir_predictor_debug_read": (c_int32, [c_void_p, c_char_p, c_void_p, c_int64, c_void_p]),
+    "ucdir_lpips_create": (c_int32, [c_int32, POINTER(c_void_p)]),
+    "ucdir_lpips_destroy": (None, [c_void_p]),
+    "ucdir_lpips_load_weight": (c_int32, [c_void_p, c_char_p, c_void_p, POINTER(c_int64), c_int32]),
+    "ucdir_lpips_finalize": (c_int32, [c_void_p]),
+    "ucdir_lpips_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32]),
+    "ucdir_lpips_forward": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ucdir_lpips_debug_read": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_int64, c_void_p]),
     "ucdir_op_conv": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                 c_void_p]),

@@ -412,3 +412,219 @@ def niqe_device(x, params):
     """NIQE of the uint8 images tensor2img_u8_device makes of ``x``, (B, C, H, W) or (C, H, W) fp32 CUDA tensors in [-1, 1], with the
     image-sized work on the GPU: a list of floats, one per image.  The 36 x 36 algebra of step 6 stays on the host."""
     return [niqe_from_features(f, params) for f in niqe_features_device(x, params).numpy()]
+
+
+# ---- LPIPS (AlexNet variant), the full-reference perceptual score of the reference's eval1.py ------------------------------------
+# The definition (DESIGN.md §4.17): x = q / 127.5 - 1, (x - shift) / scale, the five ReLU taps of torchvision's AlexNet
+# ``features``, unit-normalised over channels, squared difference weighted by the 1x1 ``lin`` layers, spatial mean, summed over the
+# taps.  No weights ship: load_lpips_weights reads the user's files.  calculate_lpips is the host path in torch CPU ops (float64:
+# the tests' oracle of csrc/lpips.hip.h), lpips_device the same arithmetic on the GPU.
+LPIPS_SHIFT = (-0.030, -0.088, -0.188)
+LPIPS_SCALE = (0.458, 0.448, 0.450)
+# (state-dict prefix, Cin, Cout, kernel, stride, pad, 3/2 max pool in front)
+LPIPS_LAYERS = (("features.0", 3, 64, 11, 4, 2, False), ("features.3", 64, 192, 5, 1, 2, True), ("features.6", 192, 384, 3, 1, 1, True),
+                ("features.8", 384, 256, 3, 1, 1, False), ("features.10", 256, 256, 3, 1, 1, False))
+LPIPS_MIN_SIDE = 31
+_lpips_handles = {}
+
+
+def lpips_weight_shapes():
+    """Name -> shape of the 15 tensors LPIPS-alex needs (the ``lin`` weights may also come as (1, C, 1, 1))."""
+    out = {}
+    for l, (key, cin, cout, k, _, _, _) in enumerate(LPIPS_LAYERS):
+        out[key + ".weight"] = (cout, cin, k, k)
+        out[key + ".bias"] = (cout,)
+        out[f"lin{l}.model.1.weight"] = (cout,)
+    return out
+
+
+def load_lpips_weights(paths):
+    """The LPIPS-alex tensors from one or more ``.npz`` / ``.pth`` files, merged (later files win): torchvision's AlexNet state dict
+    (``features.N.weight`` / ``.bias``) and the lpips package's ``alex.pth`` (``linL.model.1.weight``) are the two files in the wild.
+    Keys it does not need are ignored; a missing file or tensor stops with a message that names it.  Returns name -> float32 array."""
+    import os
+    if isinstance(paths, (str, bytes, os.PathLike)):
+        paths = [paths]
+    paths = [os.fspath(p) for p in paths]
+    if not paths:
+        raise ValueError("load_lpips_weights needs at least one file (--lpips-weights)")
+    need = lpips_weight_shapes()
+    found = {}
+    for path in paths:
+        if not os.path.isfile(path):
+            raise FileNotFoundError(f"LPIPS weight file {path!r} is missing (pass torchvision's AlexNet state dict and the lpips package's "
+                                    "alex.pth, as .pth or .npz, with --lpips-weights)")
+        if path.endswith(".npz"):
+            with np.load(path) as z:
+                sd = {k: z[k] for k in z.files if k in need}
+        else:
+            import torch
+            sd = torch.load(path, map_location="cpu", weights_only=True)
+            sd = {k: v.detach().cpu().numpy() for k, v in sd.items() if k in need}
+        found.update(sd)
+    out = {}
+    for name, shape in need.items():
+        if name not in found:
+            raise KeyError(f"LPIPS tensor {name!r} is in none of {paths}")
+        a = np.asarray(found[name], np.float32)
+        if name.startswith("lin") and a.shape == (1, shape[0], 1, 1):
+            a = a.reshape(shape)
+        if a.shape != shape:
+            raise ValueError(f"LPIPS tensor {name!r} has shape {a.shape}, expected {shape}")
+        out[name] = np.ascontiguousarray(a)
+    return out
+
+
+def _lpips_check_images(img1, img2):
+    a, b = np.asarray(img1), np.asarray(img2)
+    if a.dtype != np.uint8 or b.dtype != np.uint8:
+        raise ValueError(f"LPIPS takes uint8 images, got {a.dtype} and {b.dtype}")
+    if a.ndim != 3 or a.shape[2] != 3 or a.shape != b.shape:
+        raise ValueError(f"LPIPS takes two (H, W, 3) images of equal size, got {a.shape} and {b.shape}")
+    if a.shape[0] < LPIPS_MIN_SIDE or a.shape[1] < LPIPS_MIN_SIDE:
+        raise ValueError(f"LPIPS needs at least {LPIPS_MIN_SIDE} pixels on each side, got {a.shape[0]} x {a.shape[1]}")
+    return a, b
+
+
+def lpips_features_host(img_u8, weights, dtype=None):
+    """The five ReLU feature maps, each (C_l, H_l, W_l), of one uint8 RGB (H, W, 3) image, in torch CPU ops of ``dtype`` (default
+    float32)."""
+    import torch
+    import torch.nn.functional as F
+    dtype = dtype or torch.float32
+    img, _ = _lpips_check_images(img_u8, img_u8)
+    x = torch.from_numpy(np.ascontiguousarray(img)).permute(2, 0, 1).to(dtype) / 127.5 - 1
+    x = (x - torch.tensor(LPIPS_SHIFT, dtype=dtype).view(3, 1, 1)) / torch.tensor(LPIPS_SCALE, dtype=dtype).view(3, 1, 1)
+    x = x.unsqueeze(0)
+    feats = []
+    for key, _, _, _, stride, pad, pool in LPIPS_LAYERS:
+        if pool:
+            x = F.max_pool2d(x, 3, 2)
+        w = torch.from_numpy(weights[key + ".weight"]).to(dtype)
+        b = torch.from_numpy(weights[key + ".bias"]).to(dtype)
+        x = F.relu(F.conv2d(x, w, b, stride=stride, padding=pad))
+        feats.append(x[0])
+    return feats
+
+
+def lpips_from_features(f0, f1, weights):
+    """The five per-layer distances of two feature lists, as a tensor of the features' dtype."""
+    import torch
+    out = []
+    for l, (a, b) in enumerate(zip(f0, f1)):
+        lin = torch.from_numpy(weights[f"lin{l}.model.1.weight"]).to(a.dtype).view(-1, 1, 1)
+        na = a / (torch.sqrt(torch.sum(a * a, dim=0, keepdim=True)) + 1e-10)
+        nb = b / (torch.sqrt(torch.sum(b * b, dim=0, keepdim=True)) + 1e-10)
+        out.append(torch.sum(lin * (na - nb) ** 2, dim=0).mean())
+    return torch.stack(out)
+
+
+def calculate_lpips(img1_u8, img2_u8, weights, dtype=None, return_layers=False):
+    """LPIPS-alex of two uint8 RGB (H, W, 3) images on the host; ``dtype=torch.float64`` is the tests' oracle.  With
+    ``return_layers`` also the five per-layer distances."""
+    a, b = _lpips_check_images(img1_u8, img2_u8)
+    d = lpips_from_features(lpips_features_host(a, weights, dtype), lpips_features_host(b, weights, dtype), weights).double()
+    score = float(d.sum())
+    return (score, d.numpy()) if return_layers else score
+
+
+class LpipsDevice:
+    """The device object of csrc/lpips.hip.h: packed weights on one GPU.  ``forward`` scores (B, H, W, 3) uint8 CUDA batches."""
+
+    def __init__(self, weights, device):
+        import ctypes
+        from . import lib
+        self._lib = L = lib.load()
+        self.device = device
+        h = ctypes.c_void_p()
+        lib.check(L.ucdir_lpips_create(device.index if device.index is not None else 0, ctypes.byref(h)))
+        self._h = h
+        for name, shape in lpips_weight_shapes().items():
+            if name not in weights:
+                raise KeyError(f"LPIPS tensor {name!r} is missing from the weights")
+            a = np.ascontiguousarray(weights[name], np.float32)
+            sh = (ctypes.c_int64 * a.ndim)(*a.shape)
+            lib.check(L.ucdir_lpips_load_weight(h, name.encode(), a.ctypes.data, sh, a.ndim))
+        lib.check(L.ucdir_lpips_finalize(h))
+        self._ws = None
+
+    def forward(self, a_u8, b_u8):
+        """(scores (B), per_layer (B, 5)) float64 CUDA tensors; asynchronous on the current stream."""
+        import torch
+        from . import lib
+        from .ucdir import _ptr, _stream_ptr
+        for t in (a_u8, b_u8):
+            if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.uint8:
+                raise ValueError("LPIPS on the device takes uint8 tensors on the GPU")
+            if t.dim() != 4 or t.shape[-1] != 3 or not t.is_contiguous():
+                raise ValueError(f"LPIPS on the device takes contiguous (B, H, W, 3) images, got {tuple(t.shape)}")
+        if a_u8.shape != b_u8.shape or a_u8.device != b_u8.device or a_u8.device != self.device:
+            raise ValueError("LPIPS on the device takes two batches of equal shape on the object's device")
+        B, H, W, _ = a_u8.shape
+        nbytes = self._lib.ucdir_lpips_workspace_bytes(B, H, W)
+        if nbytes < 0:
+            raise ValueError(f"LPIPS needs at least {LPIPS_MIN_SIDE} pixels on each side, got {H} x {W} (batch {B})")
+        self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)       # kept: debug_read reads the features out of it
+        out = torch.empty(B * 6, dtype=torch.float64, device=self.device)
+        lib.check(self._lib.ucdir_lpips_forward(self._h, _ptr(a_u8), _ptr(b_u8), B, H, W, _ptr(out), _ptr(out[B:]), _ptr(self._ws),
+                                                _stream_ptr(self.device)))
+        self._shape = (B, H, W)
+        return out[:B], out[B:].view(B, 5)
+
+    def debug_read(self, layer, which):
+        """ReLU features of tap ``layer`` of the last forward's first (0) / second (1) input: (B, C, H_l, W_l) fp32 CUDA tensor."""
+        import torch
+        from . import lib
+        from .ucdir import _ptr, _stream_ptr
+        if self._ws is None:
+            raise RuntimeError("LpipsDevice.debug_read: no forward has run")
+        if layer not in range(5) or which not in (0, 1):
+            raise ValueError(f"LpipsDevice.debug_read: layer must lie in 0..4 and which be 0 or 1, got {layer!r}, {which!r}")
+        B, h, w = self._shape
+        for _, _, _, k, stride, pad, pool in LPIPS_LAYERS[:layer + 1]:
+            if pool:
+                h, w = (h - 3) // 2 + 1, (w - 3) // 2 + 1
+            h, w = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
+        dst = torch.empty((B, LPIPS_LAYERS[layer][2], h, w), dtype=torch.float32, device=self.device)
+        lib.check(self._lib.ucdir_lpips_debug_read(self._h, layer, which, _ptr(dst), dst.numel(), _stream_ptr(self.device)))
+        return dst
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._lib.ucdir_lpips_destroy(h)
+
+
+def lpips_handle(weights, device):
+    """The LpipsDevice of (this weights dict, this device), made on first use: packing and upload happen once per run."""
+    key = (id(weights), device.index)
+    hit = _lpips_handles.get(key)
+    if hit is None or hit[0] is not weights:
+        hit = (weights, LpipsDevice(weights, device))
+        _lpips_handles[key] = hit
+    return hit[1]
+
+
+def lpips_u8_device(a_u8, b_u8, weights, return_layers=False):
+    """LPIPS-alex of (B, H, W, 3) uint8 CUDA batches on the GPU: a list of floats, one per pair; one device-to-host copy."""
+    scores, layers = lpips_handle(weights, a_u8.device).forward(a_u8, b_u8)
+    host = scores.cpu().tolist()
+    return (host, layers.cpu().numpy()) if return_layers else host
+
+
+def lpips_device(x, y, weights, return_layers=False):
+    """LPIPS-alex of the uint8 images tensor2img_u8_device makes of ``x`` and ``y``, fp32 (B, 3, H, W) or (3, H, W) CUDA tensors in
+    [-1, 1], scored on the GPU (csrc/lpips.hip.h): the same uint8 images the JPEGs are written from.  A list of floats."""
+    import torch
+    for t in (x, y):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise ValueError("lpips_device takes tensors on the GPU")
+        if t.dtype != torch.float32:
+            raise ValueError(f"lpips_device takes fp32 images, got {t.dtype}")
+    if x.dim() == 3:
+        x, y = x.unsqueeze(0), y.unsqueeze(0)
+    if x.dim() != 4 or x.shape[1] != 3 or x.shape != y.shape:
+        raise ValueError(f"lpips_device takes two (B, 3, H, W) or (3, H, W) batches of equal shape, got {tuple(x.shape)} and {tuple(y.shape)}")
+    if x.shape[2] < LPIPS_MIN_SIDE or x.shape[3] < LPIPS_MIN_SIDE:
+        raise ValueError(f"LPIPS needs at least {LPIPS_MIN_SIDE} pixels on each side, got {x.shape[2]} x {x.shape[3]}")
+    return lpips_u8_device(tensor2img_u8_batch_device(x), tensor2img_u8_batch_device(y), weights, return_layers)

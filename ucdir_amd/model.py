@@ -151,6 +151,18 @@ class DDPM:
         sr = self.SR[self.SR.shape[0] - B:] if self.SR.dim() == 4 else self.SR
         return niqe_device(sr, params)
 
+    def current_lpips(self, weights=None):
+        """LPIPS-alex of the images of the last ``test()``: the final SR block against data["HR"], scored on the GPU
+        (metrics.lpips_device) on the same uint8 quantisation as ``visuals_u8``; ``weights`` from metrics.load_lpips_weights
+        (default: ``self.lpips_weights``)."""
+        from .metrics import lpips_device
+        weights = weights if weights is not None else getattr(self, "lpips_weights", None)
+        if weights is None:
+            raise ValueError("current_lpips needs the network weights: pass weights or set DDPM.lpips_weights (metrics.load_lpips_weights)")
+        B = self.data["SR"].shape[0]
+        sr = self.SR[self.SR.shape[0] - B:] if self.SR.dim() == 4 else self.SR
+        return lpips_device(sr, self.data["HR"], weights)
+
     def load_network(self):
         """model/model.py:224-251: in val phase with EMA on, ``{prefix}_gen_ema.pth`` is loaded strict=False."""
         prefix = self.opt["path"]["resume_state"]

@@ -55,3 +55,25 @@ def synth_inputs(B: int, H: int, W: int, seed: int = 0):
     guide = np.clip(cond * 0.5 + 0.2 * g.standard_normal((B, 3, H, W)), -1, 1).astype(np.float32)
     x_t = g.standard_normal((B, 3, H, W)).astype(np.float32)
     return cond, guide, x_t
+
+
+def synth_lpips_weights(seed: int = 0, bias_shift=None) -> "OrderedDict[str, np.ndarray]":
+    """Deterministic stand-ins for the 15 LPIPS-alex tensors (metrics.lpips_weight_shapes): conv weights ~ N(0, 2 / fan_in), biases
+    ~ N(0, 0.05^2), lin ~ U[0, 2 / C) (non-negative like the trained ones, mean 1 / C).  ``bias_shift={layer: value}`` adds
+    ``value`` to the bias of conv layer ``layer`` (0..4): a negative shift empties feature pixels (the 1e-10 path of the norm)."""
+    from .metrics import lpips_weight_shapes
+    out: "OrderedDict[str, np.ndarray]" = OrderedDict()
+    shifts = dict(bias_shift or {})
+    layer = -1
+    for name, shape in lpips_weight_shapes().items():
+        g = _rng_for("lpips." + name, seed)
+        if name.startswith("lin"):
+            out[name] = (g.random(shape) * (2.0 / shape[0])).astype(np.float32)
+        elif name.endswith(".bias"):
+            out[name] = (0.05 * g.standard_normal(shape) + shifts.pop(layer, 0.0)).astype(np.float32)
+        else:
+            layer += 1
+            out[name] = (np.sqrt(2.0 / (shape[1] * shape[2] * shape[3])) * g.standard_normal(shape)).astype(np.float32)
+    if shifts:
+        raise ValueError(f"bias_shift names unknown layers {sorted(shifts)} (0..4)")
+    return out
