@@ -30,7 +30,9 @@
  *     predictor, then 50 x denoiser), or order the streams yourself;
  *   - the image entry points of the val loop take no handle and allocate nothing (the caller brings the workspace): image
  *     metrics, NIQE features, the JPEG round trip, resampling, and the baseline JPEG encoder - ucdir_jpeg_encode_workspace_bytes,
- *     ucdir_jpeg_encode_bound (size queries), ucdir_jpeg_encode_header (host only, no device needed), ucdir_jpeg_encode.
+ *     ucdir_jpeg_encode_bound (size queries), ucdir_jpeg_encode_header (host only, no device needed), ucdir_jpeg_encode, and the
+ *     baseline JPEG decoder - ucdir_jpeg_decode_info, ucdir_jpeg_decode_pack, ucdir_jpeg_decode_workspace_bytes (host only),
+ *     ucdir_jpeg_decode.
  */
 #ifndef UCDIR_HIP_H
 #define UCDIR_HIP_H
@@ -201,6 +203,40 @@ int64_t ucdir_jpeg_encode_bound(int32_t H, int32_t W, int32_t subsampling);
 int32_t ucdir_jpeg_encode_header(int32_t H, int32_t W, int32_t quality, int32_t subsampling, uint8_t* out, int32_t cap);
 int32_t ucdir_jpeg_encode(const uint8_t* in, uint8_t* out, int32_t* lengths, int32_t B, int32_t H, int32_t W,
                           int32_t quality, int32_t subsampling, int32_t bgr, void* workspace, void* stream);
+
+/* Baseline JPEG decoder of the val loop's input files (additive in ABI 5; csrc/jpeg_decode.hip.h): the (h, w, 3) uint8 pixels
+ * Pillow's Image.open(file).convert("RGB") gives, or a crop of them.  Accepted: SOF0, 8 bit, one interleaved scan of all
+ * components (Ss 0, Se 63, Ah = Al = 0), greyscale or YCbCr with chroma 1x1 and luma 1x1, 2x1 or 2x2, 8-bit DQT, any DHT (optimised
+ * tables included), DRI / RSTn; APPn and COM are skipped, EXIF orientation is ignored.  The first three calls are host only and
+ * need no device.
+ *   ucdir_jpeg_decode_info   walks the markers, never past len.  0: info_host (16 ints) holds width, height, components (1 or 3),
+ *       luma sampling h, v, restart interval in MCUs, blocks per MCU, blocks, restart segments, bytes of the packed stream,
+ *       entropy bytes, MCUs across, MCUs down, subsequences, bits per subsequence, 0.  Valid but not built, positive: 1 progressive
+ *       or any other SOF, 2 arithmetic coding, 3 12-bit samples, 4 four components or an Adobe RGB / YCCK file, 5 other sampling,
+ *       6 more than one scan, 7 16-bit quantisation tables, 8 entropy data above 2^28 bytes.  Damaged, negative: -1 no SOI, -2 a
+ *       truncated segment or bad length, -3 a missing table, -4 no SOS, -5 no EOI, -6 bad header values, -7 restart markers that
+ *       do not fit the restart interval.
+ *   ucdir_jpeg_decode_pack   writes what the kernels read in one H2D copy (layout: csrc/jpeg_decode.hip.h) into packed_host[cap];
+ *       returns the byte count (info word 9), or -1.
+ *   ucdir_jpeg_decode_workspace_bytes   size of the device workspace (16-byte aligned) for such an info, -1 on a bad one.
+ *   ucdir_jpeg_decode   packed_dev: the packed stream on the device (16-byte aligned); out: (h, w, 3) uint8 HWC, the crop
+ *       [y0, y0 + h) x [x0, x0 + w), which must lie inside the image; bgr != 0 swaps channels 0 and 2; status_dev: one int32 on
+ *       the device, 0 or the OR of damage bits (1 category out of range, 2 a code outside the table, 4 a coefficient outside
+ *       its block or segment, 8 wrong block total, 16 no fixed point, 32 bad segment table), in which case out is undefined.
+ *       One image per call; asynchronous on `stream`, no allocation.
+ *   ucdir_jpeg_decode_profile   the same decode for measurements and tests: records an event in front of and behind every stage,
+ *       WAITS for the stream, and fills stage_ms_host (4 floats: the memsets, the Huffman, the IDCT and the colour stage, in ms) and
+ *       *rounds_host (the fixed-point rounds of the restart segment that needed most, the last round that changed nothing
+ *       included). */
+int32_t ucdir_jpeg_decode_info(const uint8_t* file_host, int64_t len, int32_t* info_host);
+int64_t ucdir_jpeg_decode_pack(const uint8_t* file_host, int64_t len, uint8_t* packed_host, int64_t cap);
+int64_t ucdir_jpeg_decode_workspace_bytes(const int32_t* info_host);
+int32_t ucdir_jpeg_decode(const uint8_t* packed_dev, int64_t packed_len, const int32_t* info_host, uint8_t* out,
+                          int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t bgr, void* workspace, int32_t* status_dev,
+                          void* stream);
+int32_t ucdir_jpeg_decode_profile(const uint8_t* packed_dev, int64_t packed_len, const int32_t* info_host, uint8_t* out,
+                                  int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t bgr, void* workspace, int32_t* status_dev,
+                                  void* stream, float* stage_ms_host, int32_t* rounds_host);
 
 /* Pillow-exact image resampling of the 4x super-resolution val task (additive in ABI 5; the reference degrades every HR crop with
  * PIL.Image.resize(..., BICUBIC), data/LRHR_dataset.py:385-443): byte for byte what PIL.Image.resize makes of an 8-bit RGB image.

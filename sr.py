@@ -41,12 +41,15 @@ def item_hw(item):
     return tuple((item["SR"] if "SR" in item else item["gt"]).shape[-2:])
 
 
-def make_val_dataset(val_opt):
-    """The val loader named by ``datasets.val.datasetname`` (reference data/__init__.py:59-61; absent: PairDataset)."""
+def make_val_dataset(val_opt, decode_device="cpu"):
+    """The val loader named by ``datasets.val.datasetname`` (reference data/__init__.py:59-61; absent: PairDataset).
+    ``decode_device``: where the ImageNet loaders decode their JPEG files; PairDataset ignores it."""
     name = val_opt.get("datasetname") or "PairDataset"
     if name not in VAL_DATASETS:
         raise ValueError("datasets.val.datasetname %r is not supported by -p val (known: %s)" % (name, ", ".join(VAL_DATASETS)))
-    return VAL_DATASETS[name](val_opt["data_args"], phase="val")
+    if VAL_DATASETS[name] is PairDataset:
+        return PairDataset(val_opt["data_args"], phase="val")
+    return VAL_DATASETS[name](val_opt["data_args"], phase="val", decode_device=decode_device)
 
 
 def apply_sampler_flags(opt, args):
@@ -104,6 +107,9 @@ def make_parser():
     parser.add_argument("--jpeg-device", choices=["cpu", "gpu"], default="cpu",
                         help="write the sr / hr / lr / inf JPEGs with Pillow on the host or encode them on the GPU (HIP baseline encoder, "
                              "the same bytes)")
+    parser.add_argument("--decode-device", choices=["cpu", "gpu"], default="cpu",
+                        help="decode the input JPEGs of the ImageNet val loaders with Pillow on the host or on the GPU (HIP baseline "
+                             "decoder, the same pixels; files it does not take fall back to Pillow one by one)")
     parser.add_argument("--niqe", action="store_true",
                         help="also score the restored images with NIQE, the no-reference score of the reference's eval1.py")
     parser.add_argument("--niqe-params", type=str, default="./metric/niqe_pris_params.npz",
@@ -141,7 +147,7 @@ def main(argv=None):
     logging.getLogger("val").addHandler(fh)
 
     niqe_params = Metrics.load_niqe_params(args.niqe_params) if args.niqe else None      # a missing file stops the run here
-    val_set = make_val_dataset(opt["datasets"]["val"])
+    val_set = make_val_dataset(opt["datasets"]["val"], args.decode_device)
     if args.synthetic_weights:
         opt["path"]["resume_state"] = None
     diffusion = Model.create_model(opt)
@@ -248,6 +254,10 @@ def main(argv=None):
     if n_restored:
         logger.info("restored %d images in %.2f s on this rank (%.2f img/s, batches of up to %d)" % (n_restored, t_restore, n_restored / t_restore, args.batch))
     main.last_throughput = (n_restored, t_restore)
+    main.last_decode_fallbacks = list(getattr(val_set, "decode_fallbacks", []))
+    if args.decode_device == "gpu":
+        logger.info("decoded on the GPU; %d images fell back to Pillow%s" % (
+            len(main.last_decode_fallbacks), "".join(" [%d: %s]" % f for f in main.last_decode_fallbacks[:8])))
     main.last_groups = group_times
     acc = torch.tensor([tot_psnr, tot_ssim, float(n), tot_niqe, tot_lpips], dtype=torch.float64, device="cuda")
     if world > 1:

@@ -2,6 +2,7 @@
 // Reference semantics: model/ucdir.py:270-307 (DY3h), :122-140 (block), :165-182 (attention).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -33,6 +34,7 @@
 #include "image_metrics.hip.h"
 #include "jpeg_roundtrip.hip.h"
 #include "jpeg_encode.hip.h"
+#include "jpeg_decode.hip.h"
 #include "resample.hip.h"
 #include "niqe.hip.h"
 #include "realsr.hip.h"
@@ -2015,6 +2017,113 @@ int32_t ucdir_jpeg_encode(const uint8_t* in, uint8_t* out, int32_t* lengths, int
                        (const unsigned int*)totbits, (const unsigned int*)ffpart, header, (const int*)lengths,
                        (unsigned char*)out, stride);
     HIPC(hipGetLastError());
+    API_END
+}
+
+// Baseline JPEG decoder of the val loop's input files (csrc/jpeg_decode.hip.h).  The three host functions need no device.
+int32_t ucdir_jpeg_decode_info(const uint8_t* file_host, int64_t len, int32_t* info_host) {
+    if (!file_host || !info_host || len < 0) return jpeg_dec::BAD_SOI;
+    jpeg_dec::Parsed P;
+    const int rc = jpeg_dec::parse(file_host, len, P);
+    if (rc == 0) std::memcpy(info_host, P.info, sizeof(P.info));
+    return rc;
+}
+
+int64_t ucdir_jpeg_decode_pack(const uint8_t* file_host, int64_t len, uint8_t* packed_host, int64_t cap) {
+    if (!file_host || !packed_host || len < 0) return -1;
+    return jpeg_dec::pack(file_host, len, packed_host, cap);
+}
+
+int64_t ucdir_jpeg_decode_workspace_bytes(const int32_t* info_host) {
+    if (!info_host || !jpeg_dec::info_consistent(info_host)) return -1;
+    return jpeg_dec::layout(info_host).bytes;
+}
+
+// The checks and the launches of ucdir_jpeg_decode; ev: null, or five events recorded in front of the memsets and behind the
+// memsets, the Huffman, the IDCT and the colour launch (ucdir_jpeg_decode_profile).  Throws.
+static void jpeg_decode_run(const std::string& fn, const uint8_t* packed_dev, int64_t packed_len, const int32_t* info_host, uint8_t* out,
+                            int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t bgr, void* workspace, int32_t* status_dev,
+                            hipStream_t st, hipEvent_t* ev) {
+    using namespace jpeg_dec;
+    require(packed_dev && info_host && out && workspace && status_dev, fn + ": null argument");
+    require(info_consistent(info_host), fn + ": info is not what ucdir_jpeg_decode_info fills");
+    require(packed_len == info_host[INFO_PACKED_BYTES], fn + ": packed_len is not the info's packed byte count");
+    const int W = info_host[INFO_WIDTH], H = info_host[INFO_HEIGHT];
+    require(w >= 1 && h >= 1 && x0 >= 0 && y0 >= 0 && (int64_t)x0 + w <= W && (int64_t)y0 + h <= H, fn + ": the crop must lie inside the image");
+    require(((uintptr_t)workspace & 15) == 0 && ((uintptr_t)packed_dev & 15) == 0, fn + ": packed_dev and workspace must be 16-byte aligned");
+    require(((uintptr_t)status_dev & 3) == 0, fn + ": status_dev must be 4-byte aligned");
+    hipPointerAttribute_t pa;
+    HIPC(hipPointerGetAttributes(&pa, packed_dev));
+    require(pa.type == hipMemoryTypeDevice, fn + ": packed_dev is not a device pointer");
+    const void* others[3] = {out, workspace, status_dev};
+    const char* names[3] = {"out", "workspace", "status_dev"};
+    for (int i = 0; i < 3; ++i) {
+        hipPointerAttribute_t po;
+        HIPC(hipPointerGetAttributes(&po, others[i]));
+        require(po.type == hipMemoryTypeDevice && po.device == pa.device, fn + ": " + names[i] + " must live on the device of packed_dev");
+    }
+    const Layout l = layout(info_host);
+    DevGuard dg(pa.device);
+    unsigned char* ws = (unsigned char*)workspace;
+    short* coef = (short*)(ws + l.coef);
+    const int nblk = info_host[INFO_BLOCKS], nseg = info_host[INFO_SEGMENTS], bpm = info_host[INFO_BLOCKS_PER_MCU];
+    const int hs = info_host[INFO_HS], vs = info_host[INFO_VS], ncomp = info_host[INFO_COMPONENTS];
+    auto mark = [&](int i) { if (ev) HIPC(hipEventRecord(ev[i], st)); };
+    mark(0);
+    HIPC(hipMemsetAsync(coef, 0, (size_t)nblk * 128, st));
+    HIPC(hipMemsetAsync(status_dev, 0, 4, st));
+    mark(1);
+    hipLaunchKernelGGL(jpeg_dec_huff_kernel, dim3((unsigned)std::min(nseg, 4096)), dim3(JPEG_DEC_THREADS), 0, st, packed_dev,
+                       (unsigned int)packed_len, nseg, info_host[INFO_SUBSEQS], info_host[INFO_MCUS_X] * info_host[INFO_MCUS_Y], bpm,
+                       ncomp == 1 ? 1 : hs * vs, info_host[INFO_RESTART], coef, (uint4*)(ws + l.state), (unsigned int*)(ws + l.first),
+                       (int*)(ws + l.rounds), (int*)status_dev);
+    HIPC(hipGetLastError());
+    mark(2);
+    hipLaunchKernelGGL(jpeg_dec_idct_kernel, dim3((unsigned)((nblk + 31) / 32)), dim3(256), 0, st, (const short*)coef, packed_dev, nblk,
+                       bpm, hs, vs, info_host[INFO_MCUS_X], ws + l.planes, (int)l.yw, (int)l.yh, (int)l.cw, (int)l.ch);
+    HIPC(hipGetLastError());
+    mark(3);
+    const long long npix = (long long)w * h;
+    hipLaunchKernelGGL(jpeg_dec_colour_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, (const unsigned char*)(ws + l.planes),
+                       out, W, H, ncomp, hs, vs, (int)l.yw, (int)l.yh, (int)l.cw, (int)l.ch, x0, y0, w, h, bgr ? 1 : 0);
+    HIPC(hipGetLastError());
+    mark(4);
+}
+
+int32_t ucdir_jpeg_decode(const uint8_t* packed_dev, int64_t packed_len, const int32_t* info_host, uint8_t* out, int32_t x0, int32_t y0,
+                          int32_t w, int32_t h, int32_t bgr, void* workspace, int32_t* status_dev, void* stream) {
+    API_BEGIN
+    jpeg_decode_run("ucdir_jpeg_decode", packed_dev, packed_len, info_host, out, x0, y0, w, h, bgr, workspace, status_dev,
+                    (hipStream_t)stream, nullptr);
+    API_END
+}
+
+// The same decode with an event in front of and behind every stage; waits for the stream, then reads the four times and the
+// rounds the Huffman kernel left per segment in the workspace.
+int32_t ucdir_jpeg_decode_profile(const uint8_t* packed_dev, int64_t packed_len, const int32_t* info_host, uint8_t* out, int32_t x0,
+                                  int32_t y0, int32_t w, int32_t h, int32_t bgr, void* workspace, int32_t* status_dev, void* stream,
+                                  float* stage_ms_host, int32_t* rounds_host) {
+    struct Events {
+        hipEvent_t e[5] = {};
+        ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+    } ev;
+    API_BEGIN
+    const std::string fn("ucdir_jpeg_decode_profile");
+    require(stage_ms_host && rounds_host, fn + ": null argument");
+    // the events belong to the device the work runs on: checked again, with everything else, by jpeg_decode_run
+    require(packed_dev != nullptr, fn + ": null argument");
+    hipPointerAttribute_t pa;
+    HIPC(hipPointerGetAttributes(&pa, packed_dev));
+    require(pa.type == hipMemoryTypeDevice, fn + ": packed_dev is not a device pointer");
+    DevGuard dg(pa.device);
+    for (hipEvent_t& x : ev.e) HIPC(hipEventCreate(&x));
+    jpeg_decode_run(fn, packed_dev, packed_len, info_host, out, x0, y0, w, h, bgr, workspace, status_dev, (hipStream_t)stream, ev.e);
+    HIPC(hipEventSynchronize(ev.e[4]));
+    for (int i = 0; i < 4; ++i) HIPC(hipEventElapsedTime(&stage_ms_host[i], ev.e[i], ev.e[i + 1]));
+    const int nseg = info_host[jpeg_dec::INFO_SEGMENTS];
+    std::vector<int32_t> r((size_t)nseg);
+    HIPC(hipMemcpy(r.data(), (const unsigned char*)workspace + jpeg_dec::layout(info_host).rounds, (size_t)nseg * 4, hipMemcpyDeviceToHost));
+    *rounds_host = *std::max_element(r.begin(), r.end());
     API_END
 }
 

@@ -2,7 +2,9 @@
 sorted file lists of dataroot.lq / dataroot.gt, RGB, scaled to [-1, 1] (data/util.py:76-83), dict with 'HR', 'SR', 'LR',
 'Index'; the JPEG-restoration loader ImagenetJPGDataset (reference: data/LRHR_dataset.py:446-516); and the 4x super-resolution
 loader ImagenetSRDataset (reference: data/LRHR_dataset.py:385-443); and the real-world SR loader RealESRGANDataset (reference:
-data/LRHR_dataset.py:668-807)."""
+data/LRHR_dataset.py:668-807).  The three ImageNet loaders take ``decode_device``: "cpu" (the default) decodes the file with
+Pillow on the host and uploads the pixels; "gpu" uploads the file's bytes and decodes them with csrc/jpeg_decode.hip.h, the same
+pixels, falling back to Pillow per image for what that decoder does not take (``decode_fallbacks``)."""
 import os
 
 import numpy as np
@@ -47,11 +49,50 @@ _U8_TO_UNIT = torch.from_numpy(np.arange(256, dtype=np.float32) / 255.0) * 2.0 -
 _unit_tables = {}
 
 
+def _check_decode_device(v):
+    if v not in ("cpu", "gpu"):
+        raise ValueError("decode_device must be 'cpu' or 'gpu', got %r" % (v,))
+    return v
+
+
+def decode_u8_device(ds, i, region, dev):
+    """The ``decode_device = "gpu"`` half of the ImageNet loaders: read the bytes of image ``i`` of loader ``ds`` and decode them on
+    ``dev`` (csrc/jpeg_decode.hip.h, byte for byte Pillow's convert("RGB")).  ``region(w, h)`` -> None for the whole image or the
+    (left, top, width, height) crop the loader takes of a w x h image.  Returns (uint8 CUDA tensor, whether it is already cropped),
+    or None for a file the decoder does not take (not a JPEG, progressive, CMYK, damaged, ...): the loader then decodes that image
+    with Pillow, and ``ds.decode_fallbacks`` gains (index, reason)."""
+    from .metrics import JpegUnsupported, jpeg_decode_device, jpeg_info
+    with open(ds.hr_path[i], "rb") as f:
+        data = f.read()
+    try:
+        info = jpeg_info(data)
+        crop = region(info["width"], info["height"])
+        if crop is not None and (crop[2] < 1 or crop[3] < 1):
+            raise JpegUnsupported(0, "the loader's crop of this image is empty")
+        return jpeg_decode_device(data, crop=crop, device=dev), crop is not None
+    except JpegUnsupported as e:
+        ds.decode_fallbacks.append((i, e.reason))
+        return None
+
+
 def _u8_to_unit(x):
     """(H, W, 3) uint8 on a device -> (3, H, W) fp32 in [-1, 1] on that device."""
     lut = _unit_tables.get(x.device)
     if lut is None:
         lut = _unit_tables[x.device] = _U8_TO_UNIT.to(x.device)
+    return lut[x.long()].permute(2, 0, 1).contiguous()
+
+
+_U8_TO_01 = torch.from_numpy(np.arange(256, dtype=np.float32) / 255.0)
+_01_tables = {}
+
+
+def _u8_to_01(x):
+    """(H, W, 3) uint8 on a device -> (3, H, W) fp32 in [0, 1] there, u8 / 255 as numpy float32 forms it on the host (a table, for the
+    reason _U8_TO_UNIT is one)."""
+    lut = _01_tables.get(x.device)
+    if lut is None:
+        lut = _01_tables[x.device] = _U8_TO_01.to(x.device)
     return lut[x.long()].permute(2, 0, 1).contiguous()
 
 
@@ -64,7 +105,7 @@ class ImagenetJPGDataset:
     generator seeded by the image index, not from numpy's global RNG as the reference does, so an image's degradation does not
     depend on rank, batch or order."""
 
-    def __init__(self, data_args, phase="val"):
+    def __init__(self, data_args, phase="val", decode_device="cpu"):
         root = data_args["dataroot"]
         self.root = root["root"]
         with open(root["txt"]) as f:
@@ -76,6 +117,8 @@ class ImagenetJPGDataset:
         self.sr_path = self.hr_path                  # sr.py names its outputs after sr_path
         self.crop_size = data_args.get("crop_size") or 0
         self.factor = list(data_args.get("factor") or [5, 5])
+        self.decode_device = _check_decode_device(decode_device)
+        self.decode_fallbacks = []                   # (index, reason) of every image "gpu" had to leave to Pillow
 
     def __len__(self):
         return len(self.hr_path)
@@ -94,6 +137,24 @@ class ImagenetJPGDataset:
         img = img.crop((left, top, left + cw, top + ch))
         return np.array(img, dtype=np.uint8)             # a writable copy (torch.from_numpy of PIL's read-only view warns)
 
+    def load_u8_device(self, i, dev):
+        """load_u8 with the decode on the GPU -> the same (H, W, 3) uint8 image as a tensor on ``dev``.  The centred crop is taken
+        inside the decoder; an image below crop_size is decoded whole and resized there first (Pillow's resize default, bicubic)."""
+        from .metrics import resample_device
+        cs = self.crop_size
+
+        def region(w, h):
+            if min(w, h) < cs:
+                return None
+            cw, ch = (cs, cs) if cs > 0 else (w // 16 * 16, h // 16 * 16)
+            return (w - cw) // 2, (h - ch) // 2, cw, ch
+
+        got = decode_u8_device(self, i, region, dev)
+        if got is None:
+            return torch.from_numpy(self.load_u8(i)).to(dev)
+        img, cropped = got
+        return img if cropped else resample_device(img, (cs, cs), "bicubic")       # the crop of a cs x cs image is all of it
+
     def quality(self, i):
         lo, hi = int(self.factor[0]), int(self.factor[1])
         if lo == hi:
@@ -102,7 +163,8 @@ class ImagenetJPGDataset:
 
     def __getitem__(self, i):
         from .metrics import jpeg_roundtrip_device
-        hr_u8 = torch.from_numpy(self.load_u8(i)).to(torch.device("cuda", torch.cuda.current_device()))
+        dev = torch.device("cuda", torch.cuda.current_device())
+        hr_u8 = self.load_u8_device(i, dev) if self.decode_device == "gpu" else torch.from_numpy(self.load_u8(i)).to(dev)
         sr_u8 = jpeg_roundtrip_device(hr_u8, self.quality(i), bgr=True)
         sr = _u8_to_unit(sr_u8)
         return {"HR": _u8_to_unit(hr_u8), "SR": sr, "LR": sr, "Index": i}
@@ -129,7 +191,7 @@ class ImagenetSRDataset:
     image of the last item stays reachable as ``last_lr64``."""
     sizes = (64, 256)
 
-    def __init__(self, data_args, phase="val"):
+    def __init__(self, data_args, phase="val", decode_device="cpu"):
         root = data_args["dataroot"]
         self.root = root["root"]
         with open(root["txt"]) as f:
@@ -140,6 +202,8 @@ class ImagenetSRDataset:
         self.hr_path = [os.path.join(self.root, s) for s in names]
         self.sr_path = self.hr_path                  # sr.py names its outputs after sr_path
         self.last_lr64 = None
+        self.decode_device = _check_decode_device(decode_device)
+        self.decode_fallbacks = []                   # (index, reason) of every image "gpu" had to leave to Pillow
 
     def __len__(self):
         return len(self.hr_path)
@@ -161,8 +225,14 @@ class ImagenetSRDataset:
         lr64 = resample_device(hr, (lo, lo), "bicubic")
         return hr, lr64, resample_device(lr64, (hi, hi), "bicubic")
 
+    def load_u8_device(self, i, dev):
+        """load_u8 with the decode on the GPU: the whole image, as degrade_u8 takes it."""
+        got = decode_u8_device(self, i, lambda w, h: None, dev)
+        return torch.from_numpy(self.load_u8(i)).to(dev) if got is None else got[0]
+
     def __getitem__(self, i):
-        img = torch.from_numpy(self.load_u8(i)).to(torch.device("cuda", torch.cuda.current_device()))
+        dev = torch.device("cuda", torch.cuda.current_device())
+        img = self.load_u8_device(i, dev) if self.decode_device == "gpu" else torch.from_numpy(self.load_u8(i)).to(dev)
         hr_u8, self.last_lr64, sr_u8 = self.degrade_u8(img)
         sr = _u8_to_unit(sr_u8)
         return {"HR": _u8_to_unit(hr_u8), "SR": sr, "LR": sr, "Index": i}
@@ -171,14 +241,17 @@ class ImagenetSRDataset:
 def reflect101_pad(img, size):
     """Pad an (H, W, 3) array bottom and right up to ``size`` like cv2.copyMakeBorder(..., BORDER_REFLECT_101): the mirror does not
     repeat the edge and starts over when the image is shorter than the pad."""
-    def idx(n):
-        if n >= size:
-            return np.arange(n)
-        if n == 1:
-            return np.zeros(size, dtype=np.int64)
-        i = np.arange(size) % (2 * n - 2)
-        return np.where(i < n, i, 2 * n - 2 - i)
-    return img[idx(img.shape[0])][:, idx(img.shape[1])]
+    return img[reflect101_index(img.shape[0], size)][:, reflect101_index(img.shape[1], size)]
+
+
+def reflect101_index(n, size):
+    """Source index of every row (column) of an axis of n samples padded at its end up to ``size`` by reflect101_pad's rule."""
+    if n >= size:
+        return np.arange(n)
+    if n == 1:
+        return np.zeros(size, dtype=np.int64)
+    i = np.arange(size) % (2 * n - 2)
+    return np.where(i < n, i, 2 * n - 2 - i)
 
 
 class RealESRGANDataset:
@@ -192,7 +265,7 @@ class RealESRGANDataset:
     order.  ``data_args.dopt`` / ``data_args.param``: the degradation and kernel settings, a name from
     config/realsr_degradations.yaml or a dict."""
 
-    def __init__(self, data_args, phase="val"):
+    def __init__(self, data_args, phase="val", decode_device="cpu"):
         from .degradations import load_settings
         root = data_args["dataroot"]
         if "root" not in root or "txt" not in root:
@@ -211,6 +284,8 @@ class RealESRGANDataset:
             raise ValueError("RealESRGANDataset: crop_size must be a multiple of 4 and at least 32, got %d" % self.crop_size)
         self.dopt = load_settings(data_args.get("dopt") or "dopt")
         self.kopt = load_settings(data_args.get("param") or "param")
+        self.decode_device = _check_decode_device(decode_device)
+        self.decode_fallbacks = []                   # (index, reason) of every image "gpu" had to leave to Pillow
 
     def __len__(self):
         return len(self.hr_path)
@@ -223,9 +298,29 @@ class RealESRGANDataset:
         top, left = (img.shape[0] - cs) // 2, (img.shape[1] - cs) // 2
         return np.ascontiguousarray(img[top:top + cs, left:left + cs])
 
+    def load_u8_device(self, i, dev):
+        """load_u8 with the decode on the GPU -> the same (crop_size, crop_size, 3) uint8 image as a tensor on ``dev``.  An image
+        that covers the crop is cropped inside the decoder; a smaller one is decoded whole, then padded and cropped there by
+        gathering the rows and columns reflect101_index names."""
+        cs = self.crop_size
+        got = decode_u8_device(self, i, lambda w, h: ((w - cs) // 2, (h - cs) // 2, cs, cs) if w >= cs and h >= cs else None, dev)
+        if got is None:
+            return torch.from_numpy(self.load_u8(i)).to(dev)
+        img, cropped = got
+        if cropped:
+            return img
+        rows, cols = reflect101_index(img.shape[0], cs), reflect101_index(img.shape[1], cs)
+        top, left = (len(rows) - cs) // 2, (len(cols) - cs) // 2
+        rows, cols = (torch.from_numpy(np.ascontiguousarray(v)).to(dev) for v in (rows[top:top + cs], cols[left:left + cs]))
+        return img.index_select(0, rows).index_select(1, cols).contiguous()
+
     def __getitem__(self, i):
         from .degradations import draw_realsr_params, realsr_degrade_device
         dev = torch.device("cuda", torch.cuda.current_device())
+        if self.decode_device == "gpu":
+            gt = _u8_to_01(self.load_u8_device(i, dev))
+            lq = realsr_degrade_device(gt.unsqueeze(0), draw_realsr_params(i, self.dopt, self.kopt), self.dopt)[0]
+            return {"gt": gt, "lq": lq, "Index": i}
         # u8 / 255 in numpy float32 on the host, as the reference forms it (a division by a scalar on the GPU can land one ulp away)
         gt = torch.from_numpy(np.ascontiguousarray((self.load_u8(i).astype(np.float32) / 255.0).transpose(2, 0, 1))).to(dev)
         lq = realsr_degrade_device(gt.unsqueeze(0), draw_realsr_params(i, self.dopt, self.kopt), self.dopt)[0]

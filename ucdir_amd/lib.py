@@ -59,6 +59,13 @@ _SIGS = {
     "ucdir_jpeg_encode_header": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32]),
     "ucdir_jpeg_encode": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
                                     c_void_p]),
+    "ucdir_jpeg_decode_info": (c_int32, [c_void_p, c_int64, c_void_p]),
+    "ucdir_jpeg_decode_pack": (c_int64, [c_void_p, c_int64, c_void_p, c_int64]),
+    "ucdir_jpeg_decode_workspace_bytes": (c_int64, [c_void_p]),
+    "ucdir_jpeg_decode": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
+                                    c_void_p, c_void_p]),
+    "ucdir_jpeg_decode_profile": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
+                                            c_void_p, c_void_p, c_void_p, c_void_p]),
     "ucdir_resample_coeffs": (c_int32, [c_int32, c_int32, c_int32, c_void_p, c_void_p, POINTER(c_int32)]),
     "ucdir_resample_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32]),
     "ucdir_resample": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),

@@ -188,6 +188,113 @@ def jpeg_encode_device(x_u8, quality=100, subsampling=0, bgr=False):
     return [packed[e - k:e] for e, k in zip(ends, n)]
 
 
+class JpegUnsupported(ValueError):
+    """A file jpeg_decode_device does not decode: ``code`` is what ucdir_jpeg_decode_info answered (positive: valid but not built,
+    negative: damaged) or, with ``device_status`` set, the damage bits the kernels found in the entropy data; ``reason`` says it
+    in words."""
+
+    def __init__(self, code, reason, device_status=False):
+        super().__init__(f"jpeg_decode_device: {reason} (code {code})")
+        self.code, self.reason, self.device_status = code, reason, device_status
+
+
+JPEG_INFO_FIELDS = ("width", "height", "components", "h_samp", "v_samp", "restart_interval", "blocks_per_mcu", "blocks", "segments",
+                    "packed_bytes", "entropy_bytes", "mcus_x", "mcus_y", "subsequences", "subsequence_bits", "reserved")
+JPEG_INFO_REASONS = {
+    1: "progressive or another SOF than baseline", 2: "arithmetic coding", 3: "12-bit samples",
+    4: "four components or an RGB / YCCK coded file", 5: "a sampling other than 4:4:4, 4:2:2 or 4:2:0", 6: "more than one scan",
+    7: "16-bit quantisation tables", 8: "entropy data above 2^28 bytes",
+    -1: "no SOI: not a JPEG file", -2: "a truncated segment or a bad length", -3: "a table the scan needs is missing",
+    -4: "no SOS", -5: "no EOI", -6: "bad header values", -7: "restart markers that do not fit the restart interval"}
+JPEG_STATUS_BITS = {1: "a category out of range", 2: "a code outside its Huffman table", 4: "a coefficient outside its block or segment",
+                    8: "a wrong block total", 16: "no fixed point", 32: "a bad segment table"}
+
+
+def _jpeg_info_words(data):
+    """(code, the 16 info words as a numpy int32 array)"""
+    from . import lib
+    if not isinstance(data, (bytes, bytearray, memoryview)):
+        raise ValueError(f"a JPEG file is given as bytes, got {type(data).__name__}")
+    buf = np.frombuffer(data, dtype=np.uint8)
+    info = np.zeros(16, dtype=np.int32)
+    src = np.ascontiguousarray(buf) if len(buf) else np.zeros(1, np.uint8)
+    return lib.load().ucdir_jpeg_decode_info(src.ctypes.data, len(buf), info.ctypes.data), info, src
+
+
+def jpeg_info(data):
+    """What ucdir_jpeg_decode_info says about the bytes of a JPEG file: a dict of JPEG_INFO_FIELDS.  Host only.  Raises
+    JpegUnsupported for every file jpeg_decode_device would not take."""
+    code, info, _ = _jpeg_info_words(data)
+    if code != 0:
+        raise JpegUnsupported(code, JPEG_INFO_REASONS.get(code, "unknown"))
+    return dict(zip(JPEG_INFO_FIELDS, info.tolist()))
+
+
+def jpeg_decode_device(data, crop=None, bgr=False, device=None):
+    """Decode the bytes of a baseline JPEG file on the GPU (csrc/jpeg_decode.hip.h): byte for byte what Pillow's
+    Image.open(...).convert("RGB") gives.  ``data``: bytes; ``crop``: None or (left, top, width, height) inside the image;
+    bgr=True swaps channels 0 and 2; ``device``: a CUDA device (default: the current one) -> an (h, w, 3) uint8 tensor there, decoded
+    on the current stream.  The host frames the file (markers, tables, byte unstuffing) and uploads it in one copy; the call waits
+    once, for the status word.  Raises JpegUnsupported for every file outside what include/ucdir_hip.h lists and for damaged
+    entropy data."""
+    import torch
+    from . import lib
+    from .ucdir import _ptr, _stream_ptr
+    code, info, src = _jpeg_info_words(data)
+    if code != 0:
+        raise JpegUnsupported(code, JPEG_INFO_REASONS.get(code, "unknown"))
+    L = lib.load()
+    W, H = int(info[0]), int(info[1])
+    if crop is None:
+        crop = (0, 0, W, H)
+    try:
+        x0, y0, w, h = crop
+        ok = all(not isinstance(v, bool) and int(v) == v for v in crop)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok or w < 1 or h < 1 or x0 < 0 or y0 < 0 or x0 + w > W or y0 + h > H:
+        raise ValueError(f"jpeg_decode_device: crop (left, top, width, height) = {crop!r} does not lie inside the {W} x {H} image")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev.type != "cuda":
+        raise ValueError(f"jpeg_decode_device decodes on a GPU, got device {dev}")
+    packed = torch.empty(int(info[9]), dtype=torch.uint8)
+    n = L.ucdir_jpeg_decode_pack(src.ctypes.data, len(data), packed.data_ptr(), packed.numel())
+    nbytes = L.ucdir_jpeg_decode_workspace_bytes(info.ctypes.data)
+    if n != packed.numel() or nbytes < 0:
+        raise lib.UcdirError("ucdir_jpeg_decode_pack / ucdir_jpeg_decode_workspace_bytes disagree with ucdir_jpeg_decode_info")
+    with torch.cuda.device(dev):
+        packed_dev = packed.to(dev)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        out = torch.empty((int(h), int(w), 3), dtype=torch.uint8, device=dev)
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+        lib.check(L.ucdir_jpeg_decode(_ptr(packed_dev), packed.numel(), info.ctypes.data, _ptr(out), int(x0), int(y0), int(w), int(h),
+                                      1 if bgr else 0, _ptr(ws), _ptr(status), _stream_ptr(dev)))
+        st = int(status.item())                        # the synchronisation
+    if st != 0:
+        raise JpegUnsupported(st, "damaged entropy data: " + ", ".join(v for k, v in JPEG_STATUS_BITS.items() if st & k), device_status=True)
+    return out
+
+
+def load_rgb_u8(path, decode_device="cpu", fallbacks=None):
+    """An image file as (H, W, 3) uint8 RGB.  "cpu": Image.open(path).convert("RGB") as a numpy array.  "gpu": the file's bytes
+    decoded by jpeg_decode_device, a tensor on the current GPU with the same pixels; a file that decoder does not take (not a JPEG,
+    progressive, ...) is decoded with Pillow and uploaded, and ``fallbacks`` (a list) gains (path, reason)."""
+    from PIL import Image
+    if decode_device not in ("cpu", "gpu"):
+        raise ValueError(f"decode_device must be 'cpu' or 'gpu', got {decode_device!r}")
+    if decode_device == "gpu":
+        import torch
+        with open(path, "rb") as f:
+            data = f.read()
+        try:
+            return jpeg_decode_device(data)
+        except JpegUnsupported as e:
+            if fallbacks is not None:
+                fallbacks.append((path, e.reason))
+            return torch.from_numpy(np.array(Image.open(path).convert("RGB"), dtype=np.uint8)).cuda()
+    return np.asarray(Image.open(path).convert("RGB"))
+
+
 RESAMPLE_FILTERS = {"box": 0, "bilinear": 1, "bicubic": 2, "lanczos": 3}
 
 
