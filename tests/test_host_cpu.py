@@ -47,6 +47,22 @@ def test_library_fails_loudly_without_gpu():
         net(torch.zeros(1, 6, 64, 64), torch.zeros(1, 1), torch.zeros(1, 3, 64, 64))
 
 
+def test_last_error_is_one_message_for_every_translation_unit():
+    """One entry point per unit of the library (engine, sampler, imaging, lpips.hip), each failing on a null argument before any
+    device call: ucdir_last_error holds that call's own message, and a failure in another unit overwrites it."""
+    L = lib.load()
+    calls = [
+        (lambda: L.ucdir_create(None, None), b"null argument"),
+        (lambda: L.ucdir_fewstep_update(None, None, None, None, 16, 1.0, 0.0, 0, 1.0, 0.0, 0.0, 0.0, 0, 0.0, 0, 0, None),
+         b"ucdir_fewstep_update: null argument"),
+        (lambda: L.ucdir_resample(None, None, 1, 8, 8, 4, 4, 2, None, None), b"ucdir_resample: null argument"),
+        (lambda: L.ucdir_lpips_finalize(None), b"ucdir_lpips_finalize: null argument"),
+    ]
+    for call, msg in calls + calls[:1]:          # ends where it began: the last unit's message is overwritten too
+        assert call() != 0
+        assert L.ucdir_last_error() == msg
+
+
 def test_layer_plan_matches_survey():
     L = unet_layers(SID)
     names = [l.name for l in L]

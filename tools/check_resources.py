@@ -1,5 +1,5 @@
-"""Build-time guard for the counted-wait kernels (round-5 advice): compile csrc/engine.hip with
--Rpass-analysis=kernel-resource-usage and compare every kernel's scratch / spill figures with the
+"""Build-time guard for the counted-wait kernels (round-5 advice): compile every unit of
+ucdir_amd/build.py SOURCES with -Rpass-analysis=kernel-resource-usage and compare every kernel's scratch / spill figures with the
 committed table profiles/kernel_resources.json.
 
 The kernels that read LDS by inline asm with hand-counted s_waitcnt (cgemm, conv_ws*, qkv_ws, flash_attn2,
@@ -33,15 +33,17 @@ def demangle(names):
 def measure():
     sys.path.insert(0, ROOT)
     from ucdir_amd import build as b
+    remarks = []
     with tempfile.TemporaryDirectory() as d:
-        cmd = [b._hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-fno-slp-vectorize",
-               "-Rpass-analysis=kernel-resource-usage", os.path.join(b.CSRC, "engine.hip"), "-o", os.path.join(d, "x.so")]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:
-            sys.stderr.write(r.stderr)
-            raise SystemExit("hipcc failed")
+        for src in b.SOURCES:
+            cmd = b.compile_cmd(src, os.path.join(d, "x.o"), ("-Rpass-analysis=kernel-resource-usage",))
+            r = subprocess.run(cmd, capture_output=True, text=True)
+            if r.returncode != 0:
+                sys.stderr.write(r.stderr)
+                raise SystemExit("hipcc failed")
+            remarks += r.stderr.split("\n")
     res, cur = {}, None
-    for line in r.stderr.split("\n"):
+    for line in remarks:
         m = re.search(r"remark:\s+Function Name: (\S+)", line)
         if m:
             cur = m.group(1)

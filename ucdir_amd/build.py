@@ -3,15 +3,17 @@ import os
 import shutil
 import subprocess
 import sys
+import tempfile
+from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libucdir_hip.so")
-SOURCES = ["engine.hip"]
+SOURCES = ["engine.hip", "sampler.hip", "imaging.hip", "lpips.hip"]      # one translation unit each, compiled concurrently
 
 
 def _deps():
-    """Every file the translation unit can include: all of csrc/ plus the public header."""
+    """Every file a translation unit can include: all of csrc/ plus the public header."""
     out = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".h", ".hpp", ".cpp"))]
     out.append(os.path.join(HERE, "..", "include", "ucdir_hip.h"))
     return out
@@ -34,25 +36,38 @@ def needs_build():
     return False
 
 
+def compile_cmd(src, out, extra_flags=()):
+    """The hipcc line that compiles one entry of SOURCES into the object file ``out``."""
+    # -fno-slp-vectorize: hipcc 7.2's SLP pass packs the fp32 statistics adds of cgemm_kernel<64> into v_pk_add_f32 /
+    # v_pk_fma_f32 with op_sel, and that code sums a few lanes wrongly and differently from run to run at the 288^2
+    # level (found by tests/test_hip_gpu.py::test_forward_bit_reproducible_at_bench_size; per-workgroup sums dumped:
+    # sum of squares bit-identical, plain sum off by 0.3 %).  Packed f32 VALU is no faster on gfx950 anyway.
+    return [_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-slp-vectorize", *extra_flags,
+            "-c", os.path.join(CSRC, src), "-o", out]
+
+
 def build(force=False, extra_flags=(), out=None, verbose=False):
-    """Compile csrc/engine.hip for gfx950.  Returns the library path; ``verbose`` says whether it compiled or reused."""
+    """Compile csrc/ for gfx950.  Returns the library path; ``verbose`` says whether it compiled or reused."""
     if out is None and not force and not needs_build():
         if verbose:
             print("libucdir_hip.so is newer than every source under csrc/ and include/: reused (not recompiled)")
         return LIB
     lib_out = out or LIB
-    # -fno-slp-vectorize: hipcc 7.2's SLP pass packs the fp32 statistics adds of cgemm_kernel<64> into v_pk_add_f32 /
-    # v_pk_fma_f32 with op_sel, and that code sums a few lanes wrongly and differently from run to run at the 288^2
-    # level (found by tests/test_hip_gpu.py::test_forward_bit_reproducible_at_bench_size; per-workgroup sums dumped:
-    # sum of squares bit-identical, plain sum off by 0.3 %).  Packed f32 VALU is no faster on gfx950 anyway.
-    cmd = [_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-fno-slp-vectorize",
-           *extra_flags, *[os.path.join(CSRC, s) for s in SOURCES], "-o", lib_out]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    if r.returncode != 0:
+    with tempfile.TemporaryDirectory() as tmp:
+        cmds = [compile_cmd(s, os.path.join(tmp, s + ".o"), extra_flags) for s in SOURCES]
+        # one hipcc per unit, all at once: never more than 16, whatever the machine reports
+        with ThreadPoolExecutor(max_workers=min(len(SOURCES), 16)) as pool:
+            runs = list(pool.map(lambda c: subprocess.run(c, capture_output=True, text=True), cmds))
+        link = [_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", *[c[-1] for c in cmds], "-o", lib_out]
+        if all(r.returncode == 0 for r in runs):
+            runs.append(subprocess.run(link, capture_output=True, text=True))
+    failed = [r for r in runs if r.returncode != 0]
+    for r in failed:
         sys.stderr.write(r.stdout + r.stderr)
+    if failed:
         raise RuntimeError("hipcc failed building libucdir_hip.so")
     if verbose:
-        print("compiled", lib_out, "with", " ".join(cmd[1:8]))
+        print("compiled", lib_out, "with", " ".join(cmds[0][1:6 + len(extra_flags)]))
     return lib_out
 
 

@@ -15,6 +15,9 @@
 // the same expression written with torch ops.  This matters beyond the last bit: the bf16 forward turns any difference in x_t
 // into a different realisation of its rounding noise at the next step.  m_prev is read only when b1 != 0 (it is uninitialised
 // before the first store).
+#pragma once
+#include "sampler.hip.h"      // normal4, sample_stream
+
 #define FEWSTEP_CLIP 1
 #define FEWSTEP_FACTORED 2
 struct FewstepCoef {

@@ -1,0 +1,118 @@
+// libucdir_hip: the samplers' elementwise updates and their in-kernel Philox noise (include/ucdir_hip.h).  Stateless entries:
+// each runs on the device its first buffer lives on.
+#include "../../include/ucdir_hip.h"
+#include "api_common.h"
+#include "sampler.hip.h"
+#include "fewstep.hip.h"
+
+extern "C" {
+
+int32_t ucdir_sampler_step(float* x_t, const float* eps, const float* noise, int64_t n, float c_recip, float c_recipm1,
+                           float coef1, float coef2, float sigma, void* stream) {
+    API_BEGIN
+    require(x_t && eps, "null argument");
+    DevGuard dg(same_device("ucdir_sampler_step", x_t, "x_t", nullptr, nullptr, 0));
+    long long blocks = (n + 255) / 256; if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(sampler_step_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x_t, eps,
+                       sigma != 0.f ? noise : nullptr, (long long)n, c_recip, c_recipm1, coef1, coef2, sigma);
+    HIPC(hipGetLastError());
+    API_END
+}
+
+// seeds_dev == nullptr: one stream of `seed` over the whole buffer; else B = n / per samples, sample b on the stream of seeds_dev[b]
+static void sampler_rng_launch(const char* who, float* x_t, const float* eps, int64_t n, float c_recip, float c_recipm1, float coef1, float coef2,
+                               float sigma, uint64_t seed, const uint64_t* seeds_dev, int64_t per, uint32_t step, void* stream) {
+    const std::string w(who);
+    require(x_t && (eps || sigma == -1.f), "null argument");
+    require(((uintptr_t)x_t & 15) == 0 && ((uintptr_t)eps & 15) == 0, w + ": buffers must be 16-byte aligned");
+    hipPointerAttribute_t pa;
+    HIPC(hipPointerGetAttributes(&pa, x_t));
+    require(pa.type == hipMemoryTypeDevice, w + ": not a device pointer");
+    if (seeds_dev) {
+        require(per > 0 && per % 4 == 0 && n % per == 0, w + ": n must be a whole number of samples of `per` elements, per a multiple of 4");
+        hipPointerAttribute_t ps;
+        HIPC(hipPointerGetAttributes(&ps, seeds_dev));
+        require(ps.type == hipMemoryTypeDevice && ps.device == pa.device, w + ": seeds must live on the device of the buffer");
+    }
+    DevGuard dg(pa.device);
+    long long blocks = ((n + 3) / 4 + 255) / 256; if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
+    if (eps) hipLaunchKernelGGL(sampler_step_rng_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x_t, eps, (long long)n,
+                                c_recip, c_recipm1, coef1, coef2, sigma, (unsigned long long)seed, step, (const unsigned long long*)seeds_dev, (long long)(per / 4));
+    else hipLaunchKernelGGL(fill_normal_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x_t, (long long)n, (unsigned long long)seed, step,
+                            (const unsigned long long*)seeds_dev, (long long)(per / 4));
+    HIPC(hipGetLastError());
+}
+
+int32_t ucdir_sampler_step_rng(float* x_t, const float* eps, int64_t n, float c_recip, float c_recipm1, float coef1, float coef2,
+                               float sigma, uint64_t seed, uint32_t step, void* stream) {
+    API_BEGIN
+    require(eps, "null argument");
+    sampler_rng_launch("ucdir_sampler_step_rng", x_t, eps, n, c_recip, c_recipm1, coef1, coef2, sigma, seed, nullptr, 0, step, stream);
+    API_END
+}
+
+int32_t ucdir_fill_normal(float* x, int64_t n, uint64_t seed, uint32_t step, void* stream) {
+    API_BEGIN
+    sampler_rng_launch("ucdir_fill_normal", x, nullptr, n, 0.f, 0.f, 0.f, 0.f, -1.f, seed, nullptr, 0, step, stream);
+    API_END
+}
+
+int32_t ucdir_sampler_step_rng_batched(float* x_t, const float* eps, int64_t n, int64_t per, float c_recip, float c_recipm1, float coef1, float coef2,
+                                       float sigma, const uint64_t* seeds_dev, uint32_t step, void* stream) {
+    API_BEGIN
+    require(eps && seeds_dev, "null argument");
+    sampler_rng_launch("ucdir_sampler_step_rng_batched", x_t, eps, n, c_recip, c_recipm1, coef1, coef2, sigma, 0, seeds_dev, per, step, stream);
+    API_END
+}
+
+int32_t ucdir_fill_normal_batched(float* x, int64_t n, int64_t per, const uint64_t* seeds_dev, uint32_t step, void* stream) {
+    API_BEGIN
+    require(seeds_dev, "null argument");
+    sampler_rng_launch("ucdir_fill_normal_batched", x, nullptr, n, 0.f, 0.f, 0.f, 0.f, -1.f, 0, seeds_dev, per, step, stream);
+    API_END
+}
+
+// the few-step samplers' fused update (csrc/fewstep.hip.h); seeds_dev == nullptr: one stream of `seed` over the whole buffer
+static void fewstep_launch(const char* who, float* x, const float* eps, float* m_prev, const float* noise, int64_t n, int64_t per,
+                           const FewstepCoef& k, uint64_t seed, const uint64_t* seeds_dev, uint32_t step, void* stream) {
+    const std::string w(who);
+    require(x && eps, w + ": null argument");
+    require(n >= 0, w + ": negative element count");
+    require(m_prev || (k.b1 == 0.f && !k.store_m), w + ": m_prev is needed when b1 != 0 or store_m is set");
+    const void* others[4] = {eps, m_prev, noise, seeds_dev};
+    const char* names[4] = {"eps", "m_prev", "noise", "seeds"};
+    const int device = same_device(w, x, "x", others, names, 4);
+    for (const void* q : {(const void*)x, (const void*)eps, (const void*)m_prev, (const void*)noise})
+        require(((uintptr_t)q & 15) == 0, w + ": buffers must be 16-byte aligned");
+    if (seeds_dev)
+        require(per > 0 && per % 4 == 0 && n % per == 0, w + ": n must be a whole number of samples of `per` elements, per a multiple of 4");
+    if (n == 0) return;
+    DevGuard dg(device);
+    long long blocks = ((n + 3) / 4 + 255) / 256; if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(fewstep_update_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, eps, m_prev, noise, (long long)n, k,
+                       (unsigned long long)seed, step, (const unsigned long long*)seeds_dev, (long long)(per / 4));
+    HIPC(hipGetLastError());
+}
+
+int32_t ucdir_fewstep_update(float* x, const float* eps, float* m_prev, const float* noise, int64_t n, float c_recip, float c_recipm1,
+                             int32_t flags, float p, float q, float r, float b1, int32_t store_m, float sigma, uint64_t seed, uint32_t step,
+                             void* stream) {
+    API_BEGIN
+    require((flags & ~(FEWSTEP_CLIP | FEWSTEP_FACTORED)) == 0, "fewstep update: unknown flags");
+    const FewstepCoef k{c_recip, c_recipm1, p, q, r, b1, sigma, flags, store_m != 0};
+    fewstep_launch("ucdir_fewstep_update", x, eps, m_prev, noise, n, 0, k, seed, nullptr, step, stream);
+    API_END
+}
+
+int32_t ucdir_fewstep_update_batched(float* x, const float* eps, float* m_prev, const float* noise, int64_t n, int64_t per, float c_recip,
+                                     float c_recipm1, int32_t flags, float p, float q, float r, float b1, int32_t store_m, float sigma,
+                                     const uint64_t* seeds_dev, uint32_t step, void* stream) {
+    API_BEGIN
+    require(seeds_dev, "ucdir_fewstep_update_batched: null seeds");
+    require((flags & ~(FEWSTEP_CLIP | FEWSTEP_FACTORED)) == 0, "fewstep update: unknown flags");
+    const FewstepCoef k{c_recip, c_recipm1, p, q, r, b1, sigma, flags, store_m != 0};
+    fewstep_launch("ucdir_fewstep_update_batched", x, eps, m_prev, noise, n, per, k, 0, seeds_dev, step, stream);
+    API_END
+}
+
+}  // extern "C"

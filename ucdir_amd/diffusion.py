@@ -169,7 +169,7 @@ class GaussianDiffusion(nn.Module):
         the update kernel (p_sample_loop without an injected noise source) and needs a seed for it."""
         self._gen = None
         # p_sample_loop draws its noise INSIDE the update kernel (counter-based Philox keyed by (seed, step, element),
-        # csrc/misc.hip.h): seed = noise_seed + image offset when set (identical on every rank), else a fresh 63-bit draw from
+        # csrc/sampler.hip.h): seed = noise_seed + image offset when set (identical on every rank), else a fresh 63-bit draw from
         # torch's CPU generator (torch.manual_seed still makes a run reproducible).  Injected noise (noise_source) bypasses it.
         if self.noise_seed is not None:
             self._kseed = int(self.noise_seed) + 1000003 * int(self.noise_index)
