@@ -32,7 +32,7 @@
  *     metrics, NIQE features, the JPEG round trip, resampling, and the baseline JPEG encoder - ucdir_jpeg_encode_workspace_bytes,
  *     ucdir_jpeg_encode_bound (size queries), ucdir_jpeg_encode_header (host only, no device needed), ucdir_jpeg_encode, and the
  *     baseline JPEG decoder - ucdir_jpeg_decode_info, ucdir_jpeg_decode_pack, ucdir_jpeg_decode_workspace_bytes (host only),
- *     ucdir_jpeg_decode.
+ *     ucdir_jpeg_decode, ucdir_jpeg_decode_batch_plan (host only), ucdir_jpeg_decode_batch.
  */
 #ifndef UCDIR_HIP_H
 #define UCDIR_HIP_H
@@ -237,6 +237,44 @@ int32_t ucdir_jpeg_decode(const uint8_t* packed_dev, int64_t packed_len, const i
 int32_t ucdir_jpeg_decode_profile(const uint8_t* packed_dev, int64_t packed_len, const int32_t* info_host, uint8_t* out,
                                   int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t bgr, void* workspace, int32_t* status_dev,
                                   void* stream, float* stage_ms_host, int32_t* rounds_host);
+
+/* Several files per call (additive in ABI 5; csrc/jpeg_decode.hip.h, "several files per call"): every restart segment of every file
+ * of a batch gets its own workgroup in one Huffman launch, and one IDCT and one colour launch run over all files, so the number
+ * of launches and memsets does not depend on n.  Files of different size, sampling, tables and crop sit side by side; each is
+ * checked against its own slices, and a damaged one sets only its own status word.
+ * The caller builds ONE host buffer and uploads it in one copy:
+ *   bytes 0 .. table_bytes        the descriptor table ucdir_jpeg_decode_batch_plan writes: a 128-byte header (magic, n, work items,
+ *                                 IDCT and colour workgroups, the offsets of the parts below, workspace, output and buffer bytes),
+ *                                 n descriptors of 128 bytes (stream, output and workspace offsets, geometry, crop), the work
+ *                                 items (file, restart segment) of 8 bytes by descending bit length (ties: file, then segment),
+ *                                 and two prefix tables of n + 1 words: IDCT workgroups (32 blocks each) and colour workgroups
+ *                                 (256 crop pixels each) in front of every file; every part 16-byte aligned
+ *   packed_off[k] ..              file k's packed stream (ucdir_jpeg_decode_pack), 16-byte aligned, behind the table
+ *   ucdir_jpeg_decode_batch_plan (host only, no device needed)   infos_host: n x 16 ints of ucdir_jpeg_decode_info; crops_host:
+ *       n x (x0, y0, w, h) or null for whole images; packed_off_host / out_off_host: n byte offsets into the buffer / into out
+ *       (file k's (h, w, 3) pixels start at out + out_off[k]).  With buffer_host null (the query form; crops and offsets may be null
+ *       too) it returns the table's byte count and stores the batch workspace's byte count in *workspace_bytes - at least the
+ *       sum of ucdir_jpeg_decode_workspace_bytes over the files.  Otherwise the packed streams must already stand in buffer_host
+ *       (buffer_bytes: table and streams, 8-byte aligned); it writes the table in front of them and returns its byte count.
+ *       Returns -1 with a message in ucdir_last_error for n < 1, n > 65536, an info block that is not what
+ *       ucdir_jpeg_decode_info fills, a crop outside its image, a stream offset that is not 16-byte aligned, lies inside the
+ *       table or outside the buffer or does not hold that info's stream, a negative output offset, a buffer smaller than the
+ *       table, and totals (segments, IDCT or colour workgroups) above 2^31 - 1; nothing is written then.
+ *   ucdir_jpeg_decode_batch   buffer_dev: the uploaded buffer (16-byte aligned); table_host: its host copy (the launches are sized
+ *       by the header there); out / out_bytes, workspace / workspace_bytes (16-byte aligned): at least what the table says;
+ *       status_dev: n int32 on the device, per file 0 or the damage bits of ucdir_jpeg_decode, in which case that file's pixels
+ *       are undefined and every other file's are not touched by it.  Two memsets and three launches; asynchronous on `stream`, no
+ *       allocation.
+ *   ucdir_jpeg_decode_batch_profile   the same for measurements and tests: WAITS, fills stage_ms_host (4 floats, as
+ *       ucdir_jpeg_decode_profile) and rounds_host (n ints: per file the fixed-point rounds of the segment that needed most). */
+int64_t ucdir_jpeg_decode_batch_plan(int32_t n, const int32_t* infos_host, const int32_t* crops_host, const int64_t* packed_off_host,
+                                     const int64_t* out_off_host, uint8_t* buffer_host, int64_t buffer_bytes, int64_t* workspace_bytes);
+int32_t ucdir_jpeg_decode_batch(const uint8_t* buffer_dev, const uint8_t* table_host, int64_t buffer_bytes, uint8_t* out,
+                                int64_t out_bytes, int32_t bgr, void* workspace, int64_t workspace_bytes, int32_t* status_dev,
+                                void* stream);
+int32_t ucdir_jpeg_decode_batch_profile(const uint8_t* buffer_dev, const uint8_t* table_host, int64_t buffer_bytes, uint8_t* out,
+                                        int64_t out_bytes, int32_t bgr, void* workspace, int64_t workspace_bytes,
+                                        int32_t* status_dev, void* stream, float* stage_ms_host, int32_t* rounds_host);
 
 /* Pillow-exact image resampling of the 4x super-resolution val task (additive in ABI 5; the reference degrades every HR crop with
  * PIL.Image.resize(..., BICUBIC), data/LRHR_dataset.py:385-443): byte for byte what PIL.Image.resize makes of an 8-bit RGB image.

@@ -110,6 +110,9 @@ def make_parser():
     parser.add_argument("--decode-device", choices=["cpu", "gpu"], default="cpu",
                         help="decode the input JPEGs of the ImageNet val loaders with Pillow on the host or on the GPU (HIP baseline "
                              "decoder, the same pixels; files it does not take fall back to Pillow one by one)")
+    parser.add_argument("--decode-batch", type=int, default=1,
+                        help="with --decode-device gpu: decode the input JPEGs of this many val images ahead in one batch call "
+                             "(1: file by file); the files, logs and scores are the same")
     parser.add_argument("--niqe", action="store_true",
                         help="also score the restored images with NIQE, the no-reference score of the reference's eval1.py")
     parser.add_argument("--niqe-params", type=str, default="./metric/niqe_pris_params.npz",
@@ -232,7 +235,12 @@ def main(argv=None):
 
     pending = {}                                                  # (H, W) -> images of this rank waiting for a full batch (first-seen order)
     nsmall = 0
-    for i in idxs:
+    ahead = args.decode_batch if args.decode_device == "gpu" and hasattr(val_set, "prefetch") else 1
+    in_flight = ()                                                # the indices the last prefetch decoded
+    for pos, i in enumerate(idxs):
+        if ahead > 1 and i not in in_flight:
+            in_flight = idxs[pos:pos + ahead]
+            val_set.prefetch(in_flight)
         item = val_set[i]
         h, w = item_hw(item)
         shared = world > 1 and (h + 128) * (w + 128) > thr        # DDPM.test pads 64 per side: this image is patch-split

@@ -340,6 +340,100 @@ int32_t ucdir_jpeg_decode_profile(const uint8_t* packed_dev, int64_t packed_len,
     API_END
 }
 
+// Several files per call (csrc/jpeg_decode.hip.h, "several files per call").  The plan is host only and needs no device.
+int64_t ucdir_jpeg_decode_batch_plan(int32_t n, const int32_t* infos_host, const int32_t* crops_host, const int64_t* packed_off_host,
+                                     const int64_t* out_off_host, uint8_t* buffer_host, int64_t buffer_bytes, int64_t* workspace_bytes) {
+    const std::string fn("ucdir_jpeg_decode_batch_plan: ");
+    jpeg_dec::BatchSizes z;
+    const char* e = jpeg_dec::batch_sizes(n, infos_host, z);
+    if (!e && buffer_host) e = jpeg_dec::batch_plan(n, infos_host, crops_host, packed_off_host, out_off_host, buffer_host, buffer_bytes);
+    if (e) {
+        fail(fn + e);
+        return -1;
+    }
+    if (workspace_bytes) *workspace_bytes = z.ws_bytes;
+    return z.table_bytes;
+}
+
+// The checks and the launches of ucdir_jpeg_decode_batch: two memsets and three launches, whatever n.  ev as in jpeg_decode_run.
+static void jpeg_decode_batch_run(const std::string& fn, const uint8_t* buffer_dev, const uint8_t* table_host, int64_t buffer_bytes,
+                                  uint8_t* out, int64_t out_bytes, int32_t bgr, void* workspace, int64_t workspace_bytes,
+                                  int32_t* status_dev, hipStream_t st, hipEvent_t* ev) {
+    using namespace jpeg_dec;
+    require(buffer_dev && table_host && out && workspace && status_dev, fn + ": null argument");
+    BatchHeader h;
+    std::memcpy(&h, table_host, sizeof(h));
+    if (const char* e = batch_header_check(h, buffer_bytes)) throw std::runtime_error(fn + ": " + e);
+    require(out_bytes >= 0 && (uint64_t)out_bytes >= h.out_bytes, fn + ": out is smaller than the table's outputs");
+    require(workspace_bytes >= 0 && (uint64_t)workspace_bytes >= h.ws_bytes, fn + ": workspace is smaller than the plan's workspace_bytes");
+    require(((uintptr_t)workspace & 15) == 0 && ((uintptr_t)buffer_dev & 15) == 0, fn + ": buffer_dev and workspace must be 16-byte aligned");
+    require(((uintptr_t)status_dev & 3) == 0, fn + ": status_dev must be 4-byte aligned");
+    const void* others[3] = {out, workspace, status_dev};
+    const char* names[3] = {"out", "workspace", "status_dev"};
+    const int device = same_device(fn, buffer_dev, "buffer_dev", others, names, 3);
+    DevGuard dg(device);
+    unsigned char* ws = (unsigned char*)workspace;
+    auto mark = [&](int i) { if (ev) HIPC(hipEventRecord(ev[i], st)); };
+    mark(0);
+    HIPC(hipMemsetAsync(ws, 0, (size_t)h.zero_bytes, st));                 // the coefficients and the rounds of every file
+    HIPC(hipMemsetAsync(status_dev, 0, (size_t)h.n * 4, st));
+    mark(1);
+    hipLaunchKernelGGL(jpeg_dec_huff_batch_kernel, dim3(std::min<unsigned>(h.nitems, BATCH_HUFF_GRID)), dim3(JPEG_DEC_THREADS), 0, st,
+                       buffer_dev, ws, (int*)status_dev);
+    HIPC(hipGetLastError());
+    mark(2);
+    hipLaunchKernelGGL(jpeg_dec_idct_batch_kernel, dim3(h.idct_wgs), dim3(256), 0, st, buffer_dev, ws);
+    HIPC(hipGetLastError());
+    mark(3);
+    hipLaunchKernelGGL(jpeg_dec_colour_batch_kernel, dim3(h.colour_wgs), dim3(256), 0, st, buffer_dev, (const unsigned char*)ws, out,
+                       bgr ? 1 : 0);
+    HIPC(hipGetLastError());
+    mark(4);
+}
+
+int32_t ucdir_jpeg_decode_batch(const uint8_t* buffer_dev, const uint8_t* table_host, int64_t buffer_bytes, uint8_t* out, int64_t out_bytes,
+                                int32_t bgr, void* workspace, int64_t workspace_bytes, int32_t* status_dev, void* stream) {
+    API_BEGIN
+    jpeg_decode_batch_run("ucdir_jpeg_decode_batch", buffer_dev, table_host, buffer_bytes, out, out_bytes, bgr, workspace, workspace_bytes,
+                          status_dev, (hipStream_t)stream, nullptr);
+    API_END
+}
+
+// The batch decode with an event in front of and behind every stage; waits, then reads the four times and, in one copy, the rounds
+// of every segment of the batch, of which every file gets its largest.
+int32_t ucdir_jpeg_decode_batch_profile(const uint8_t* buffer_dev, const uint8_t* table_host, int64_t buffer_bytes, uint8_t* out,
+                                        int64_t out_bytes, int32_t bgr, void* workspace, int64_t workspace_bytes, int32_t* status_dev,
+                                        void* stream, float* stage_ms_host, int32_t* rounds_host) {
+    struct Events {
+        hipEvent_t e[5] = {};
+        ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+    } ev;
+    API_BEGIN
+    using namespace jpeg_dec;
+    const std::string fn("ucdir_jpeg_decode_batch_profile");
+    require(stage_ms_host && rounds_host && buffer_dev && table_host, fn + ": null argument");
+    DevGuard dg(same_device(fn, buffer_dev, "buffer_dev", nullptr, nullptr, 0));
+    for (hipEvent_t& x : ev.e) HIPC(hipEventCreate(&x));
+    jpeg_decode_batch_run(fn, buffer_dev, table_host, buffer_bytes, out, out_bytes, bgr, workspace, workspace_bytes, status_dev,
+                          (hipStream_t)stream, ev.e);
+    HIPC(hipEventSynchronize(ev.e[4]));
+    for (int i = 0; i < 4; ++i) HIPC(hipEventElapsedTime(&stage_ms_host[i], ev.e[i], ev.e[i + 1]));
+    BatchHeader h;
+    std::memcpy(&h, table_host, sizeof(h));
+    std::vector<BatchFile> files(h.n);
+    std::memcpy(files.data(), table_host + sizeof(BatchHeader), (size_t)h.n * sizeof(BatchFile));
+    const uint64_t r0 = files[0].rounds_off;                               // the rounds of all files stand together, file 0's first
+    require(r0 <= h.zero_bytes && (h.zero_bytes - r0) % 4 == 0, fn + ": table_host holds no rounds region");
+    std::vector<int32_t> r((size_t)((h.zero_bytes - r0) / 4));
+    HIPC(hipMemcpy(r.data(), (const unsigned char*)workspace + r0, r.size() * 4, hipMemcpyDeviceToHost));
+    for (uint32_t k = 0; k < h.n; ++k) {
+        const uint64_t at = (files[k].rounds_off - r0) / 4;
+        require(files[k].rounds_off >= r0 && files[k].nseg >= 1 && at + (uint64_t)files[k].nseg <= r.size(), fn + ": table_host holds a rounds slice outside its region");
+        rounds_host[k] = *std::max_element(r.begin() + at, r.begin() + at + files[k].nseg);
+    }
+    API_END
+}
+
 // Pillow-exact resampling of the super-resolution val task (csrc/resample.hip.h).  Table layout in the workspace: per changing
 // axis out_size * ksize coefficients then out_size (min, count) pairs, horizontal axis first; 16-byte rounded; then the
 // intermediate image.

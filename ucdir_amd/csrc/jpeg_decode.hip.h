@@ -50,12 +50,18 @@
 // z <= 63, and sets the status instead of writing otherwise; so do a category above 11 (DC) or 10 (AC), a code that matches no
 // table entry and a segment table that points outside the workspace.  Only the writing pass, which runs on true states, reports.
 //
+// Several files per call: the *_batch_kernel forms below run the same three stages over the files of one uploaded buffer, one launch
+// each; the per-segment, per-workgroup and per-pixel bodies are the functions the single-file kernels call ("several files per
+// call" further down describes the table they read).
+//
 // Capacity: entropy data up to 2^28 bytes (bit positions are uint32), sides up to 65535 (the frame header).
 // Integer VALU and LDS only; the Huffman tables live in LDS; no per-thread arrays.
 #ifndef UCDIR_JPEG_DECODE_HIP_H
 #define UCDIR_JPEG_DECODE_HIP_H
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <vector>
 
 #define JPEG_DEC_SUBSEQ_BITS 1024                         // S: a multiple of 32
 #define JPEG_DEC_THREADS 256                              // threads of the huff kernel
@@ -483,9 +489,310 @@ inline bool info_consistent(const int32_t* i) {
     if (ent < 0 || ent > MAX_ENTROPY_BYTES || nsub < 0 || nsub > ent * 8 / JPEG_DEC_SUBSEQ_BITS + nseg) return false;
     return i[INFO_PACKED_BYTES] == OFF_SEG + 16 * nseg + (ent + 3) / 4 * 4;
 }
+
+// ---- several files per call ---------------------------------------------------------------------------------------------------
+// One buffer, uploaded in one H2D copy: the descriptor table batch_plan() writes, then the packed streams of the files (each
+// 16-byte aligned, at the offset the caller chose).  The table:
+//   bytes 0..127        BatchHeader
+//   128..               n x BatchFile (128 bytes each): where the file's stream, output and workspace slices are, its geometry, its crop
+//   off_items..         the work items of the Huffman stage, 8 bytes each: (file, restart segment), every segment of every file,
+//                       ordered by descending bit length (ties: file, then segment) so that the longest streams start first
+//   off_idct..          n + 1 words: workgroups of the IDCT stage in front of file k (32 blocks per workgroup, rounded up per file)
+//   off_colour..        n + 1 words: workgroups of the colour stage in front of file k (256 pixels of the crop each, rounded up)
+// every part 16-byte aligned.  The batch workspace: the coefficients of all files, then the rounds of all files (one memset
+// clears both; the profile call reads the rounds in one copy), then per file its states, first blocks and planes - the parts
+// layout() names, each 16-byte aligned, every file's slices disjoint from every other's.
+constexpr uint32_t BATCH_MAGIC = 0x3142444au;             // "JDB1"
+constexpr int BATCH_MAX_FILES = 65536;
+constexpr int BATCH_HUFF_GRID = 4096;                     // workgroups of a Huffman launch at most
+
+struct BatchHeader {
+    uint32_t magic, n, nitems, idct_wgs, colour_wgs, reserved;
+    uint64_t off_items, off_idct, off_colour, table_bytes, ws_bytes, zero_bytes, out_bytes, buffer_bytes;
+    uint64_t pad[5];
+};
+struct BatchFile {
+    uint64_t packed_off, out_off;                         // in the uploaded buffer; in the output buffer
+    uint64_t coef_off, state_off, first_off, rounds_off, planes_off;   // in the workspace
+    uint32_t packed_len;
+    int32_t nseg, nsub, nmcu, bpm, nluma, restart, nblk;
+    int32_t W, H, ncomp, hs, vs, mcus_x;
+    int32_t x0, y0, w, h;                                 // the crop
+};
+struct BatchItem {
+    uint32_t file, seg;
+};
+static_assert(sizeof(BatchHeader) == 128 && sizeof(BatchFile) == 128 && sizeof(BatchItem) == 8, "table layout");
+
+struct BatchSizes {
+    int64_t table_bytes, ws_bytes, nitems;
+};
+
+// The sizes of a batch of n info blocks (16 words each) -> null, or why there is no such batch.
+inline const char* batch_sizes(int64_t n, const int32_t* infos, BatchSizes& z) {
+    if (n < 1) return "n must be at least 1";
+    if (n > BATCH_MAX_FILES) return "more than 65536 files in one batch";
+    if (!infos) return "null argument";
+    int64_t nitems = 0, idct = 0, ws = 0;
+    for (int64_t k = 0; k < n; ++k) {
+        const int32_t* i = infos + k * INFO_WORDS;
+        if (!info_consistent(i)) return "an info block is not what ucdir_jpeg_decode_info fills";
+        nitems += i[INFO_SEGMENTS];
+        idct += ((int64_t)i[INFO_BLOCKS] + 31) / 32;
+        ws += layout(i).bytes;
+    }
+    if (nitems > 0x7fffffffLL || idct > 0x7fffffffLL) return "the batch's segments or blocks overflow the kernels' 32-bit indices";
+    auto up16 = [](int64_t v) { return (v + 15) / 16 * 16; };
+    z.nitems = nitems;
+    z.ws_bytes = ws;
+    z.table_bytes = (int64_t)sizeof(BatchHeader) + n * (int64_t)sizeof(BatchFile) + up16(nitems * 8) + 2 * up16((n + 1) * 4);
+    return nullptr;
+}
+
+// Writes the table into buf[0 .. table_bytes); the packed streams must already stand in buf at packed_off (their segment tables
+// give the items' order).  crops: n x (x0, y0, w, h), or null for whole images.  cap: bytes of buf, table and streams.
+inline const char* batch_plan(int64_t n, const int32_t* infos, const int32_t* crops, const int64_t* packed_off, const int64_t* out_off,
+                              uint8_t* buf, int64_t cap) {
+    BatchSizes z;
+    if (const char* e = batch_sizes(n, infos, z)) return e;
+    if (!packed_off || !out_off || !buf) return "null argument";
+    if (((uintptr_t)buf & 7) != 0) return "the buffer must be 8-byte aligned";
+    if (cap < z.table_bytes) return "the buffer is smaller than the descriptor table";
+    auto up16 = [](int64_t v) { return (v + 15) / 16 * 16; };
+    BatchHeader h;
+    std::memset(&h, 0, sizeof(h));
+    h.magic = BATCH_MAGIC;
+    h.n = (uint32_t)n;
+    h.nitems = (uint32_t)z.nitems;
+    h.off_items = sizeof(BatchHeader) + (uint64_t)n * sizeof(BatchFile);
+    h.off_idct = h.off_items + (uint64_t)up16(z.nitems * 8);
+    h.off_colour = h.off_idct + (uint64_t)up16((n + 1) * 4);
+    h.table_bytes = (uint64_t)z.table_bytes;
+    h.ws_bytes = (uint64_t)z.ws_bytes;
+    h.buffer_bytes = (uint64_t)cap;
+    // the checks first: nothing is written for a batch that is refused
+    int64_t colour = 0;
+    for (int64_t k = 0; k < n; ++k) {
+        const int32_t* i = infos + k * INFO_WORDS;
+        const int64_t x0 = crops ? crops[4 * k] : 0, y0 = crops ? crops[4 * k + 1] : 0;
+        const int64_t w = crops ? crops[4 * k + 2] : i[INFO_WIDTH], hh = crops ? crops[4 * k + 3] : i[INFO_HEIGHT];
+        if (w < 1 || hh < 1 || x0 < 0 || y0 < 0 || x0 + w > i[INFO_WIDTH] || y0 + hh > i[INFO_HEIGHT]) return "a crop does not lie inside its image";
+        if (packed_off[k] & 15) return "a packed-stream offset is not 16-byte aligned";
+        if (packed_off[k] < z.table_bytes || packed_off[k] > cap - i[INFO_PACKED_BYTES]) return "a packed stream lies outside the buffer or inside the table";
+        if (out_off[k] < 0 || out_off[k] > (1LL << 46)) return "an output offset is negative or above 2^46";
+        if (std::memcmp(buf + packed_off[k], i, 64) != 0) return "the bytes at a packed-stream offset are not that info's packed stream";
+        colour += (w * hh + 255) / 256;
+        h.out_bytes = std::max<uint64_t>(h.out_bytes, (uint64_t)(out_off[k] + 3 * w * hh));
+    }
+    if (colour > 0x7fffffffLL) return "the batch's pixels overflow the kernels' 32-bit indices";
+    BatchFile* files = reinterpret_cast<BatchFile*>(buf + sizeof(BatchHeader));
+    BatchItem* items = reinterpret_cast<BatchItem*>(buf + h.off_items);
+    uint32_t* idct_wg = reinterpret_cast<uint32_t*>(buf + h.off_idct);
+    uint32_t* colour_wg = reinterpret_cast<uint32_t*>(buf + h.off_colour);
+    std::memset(buf + h.off_items, 0, (size_t)(h.table_bytes - h.off_items));
+    int64_t at = 0;
+    for (int64_t k = 0; k < n; ++k) {                     // the coefficients of all files, then the rounds of all files
+        files[k].coef_off = (uint64_t)at;
+        at += up16((int64_t)infos[k * INFO_WORDS + INFO_BLOCKS] * 128);
+    }
+    for (int64_t k = 0; k < n; ++k) {
+        files[k].rounds_off = (uint64_t)at;
+        at += up16((int64_t)infos[k * INFO_WORDS + INFO_SEGMENTS] * 4);
+    }
+    h.zero_bytes = (uint64_t)at;
+    struct Key { uint32_t bits, file, seg; };
+    std::vector<Key> keys;
+    keys.reserve((size_t)z.nitems);
+    uint32_t nidct = 0, ncolour = 0;
+    for (int64_t k = 0; k < n; ++k) {
+        const int32_t* i = infos + k * INFO_WORDS;
+        const Layout l = layout(i);
+        BatchFile& f = files[k];
+        f.packed_off = (uint64_t)packed_off[k];
+        f.out_off = (uint64_t)out_off[k];
+        f.state_off = (uint64_t)at;
+        f.first_off = f.state_off + (uint64_t)(l.first - l.state);
+        f.planes_off = f.first_off + (uint64_t)(l.rounds - l.first);
+        at = (int64_t)f.planes_off + (l.bytes - l.planes);
+        f.packed_len = (uint32_t)i[INFO_PACKED_BYTES];
+        f.nseg = i[INFO_SEGMENTS];
+        f.nsub = i[INFO_SUBSEQS];
+        f.nmcu = i[INFO_MCUS_X] * i[INFO_MCUS_Y];
+        f.bpm = i[INFO_BLOCKS_PER_MCU];
+        f.nluma = i[INFO_COMPONENTS] == 1 ? 1 : i[INFO_HS] * i[INFO_VS];
+        f.restart = i[INFO_RESTART];
+        f.nblk = i[INFO_BLOCKS];
+        f.W = i[INFO_WIDTH];
+        f.H = i[INFO_HEIGHT];
+        f.ncomp = i[INFO_COMPONENTS];
+        f.hs = i[INFO_HS];
+        f.vs = i[INFO_VS];
+        f.mcus_x = i[INFO_MCUS_X];
+        f.x0 = crops ? crops[4 * k] : 0;
+        f.y0 = crops ? crops[4 * k + 1] : 0;
+        f.w = crops ? crops[4 * k + 2] : f.W;
+        f.h = crops ? crops[4 * k + 3] : f.H;
+        idct_wg[k] = nidct;
+        colour_wg[k] = ncolour;
+        nidct += (uint32_t)(((int64_t)f.nblk + 31) / 32);
+        ncolour += (uint32_t)(((int64_t)f.w * f.h + 255) / 256);
+        for (int32_t s = 0; s < f.nseg; ++s) {            // inside the stream: info_consistent ties packed_len to nseg
+            uint32_t bits;
+            std::memcpy(&bits, buf + packed_off[k] + OFF_SEG + 16 * (int64_t)s + 4, 4);
+            keys.push_back({bits, (uint32_t)k, (uint32_t)s});
+        }
+    }
+    idct_wg[n] = h.idct_wgs = nidct;
+    colour_wg[n] = h.colour_wgs = ncolour;
+    std::sort(keys.begin(), keys.end(), [](const Key& a, const Key& b) {
+        return a.bits != b.bits ? a.bits > b.bits : a.file != b.file ? a.file < b.file : a.seg < b.seg;
+    });
+    for (size_t j = 0; j < keys.size(); ++j) items[j] = {keys[j].file, keys[j].seg};
+    std::memcpy(buf, &h, sizeof(h));
+    return at == z.ws_bytes ? nullptr : "internal: the workspace slices do not add up";
+}
+
+// what ucdir_jpeg_decode_batch believes of the host copy of a table: the counts its launches are sized by
+inline const char* batch_header_check(const BatchHeader& h, int64_t buffer_bytes) {
+    if (h.magic != BATCH_MAGIC) return "table_host is not what ucdir_jpeg_decode_batch_plan wrote";
+    const uint64_t n = h.n;
+    if (n < 1 || n > (uint64_t)BATCH_MAX_FILES || h.nitems < n || h.nitems > 0x7fffffffu || h.idct_wgs < n || h.idct_wgs > 0x7fffffffu ||
+        h.colour_wgs < n || h.colour_wgs > 0x7fffffffu)
+        return "table_host holds counts outside the kernels' range";
+    if (h.off_items != 128 + 128 * n || h.off_idct != h.off_items + ((uint64_t)h.nitems * 8 + 15) / 16 * 16 ||
+        h.off_colour != h.off_idct + ((n + 1) * 4 + 15) / 16 * 16 || h.table_bytes != h.off_colour + ((n + 1) * 4 + 15) / 16 * 16)
+        return "table_host holds offsets that do not follow from its counts";
+    if (buffer_bytes < 0 || h.buffer_bytes != (uint64_t)buffer_bytes || h.table_bytes > h.buffer_bytes || h.zero_bytes > h.ws_bytes)
+        return "buffer_bytes is not the size the table was planned for";
+    return nullptr;
+}
 }  // namespace jpeg_dec
 
 #if defined(__HIPCC__)
+// What the Huffman stage knows of one file: its packed stream, the sizes its loops and checks go by, and its workspace slices.
+struct JpegDecHuffFile {
+    const unsigned char* packed;
+    int nseg, nsub_total, nmcu, bpm, nluma, restart;
+    short* coef;
+    uint4* state;
+    unsigned int* first;
+    int* rounds;
+};
+
+// The file's four Huffman tables and block selectors into LDS and its stream into s.  The caller puts a barrier behind it, and
+// one in front of it where the tables of another file may still be in use.
+__device__ inline void jpeg_dec_huff_load(const JpegDecHuffFile& f, unsigned int packed_len, jpeg_dec::HuffTable* tab, unsigned char* bsel,
+                                          jpeg_dec::Stream& s) {
+    using namespace jpeg_dec;
+    const int tid = threadIdx.x;
+    const unsigned int* src = reinterpret_cast<const unsigned int*>(f.packed + OFF_HUFF);
+    unsigned int* dst = reinterpret_cast<unsigned int*>(tab);
+    for (int i = tid; i < (int)(4 * sizeof(HuffTable) / 4); i += JPEG_DEC_THREADS) dst[i] = src[i];
+    if (tid < 8) {                                        // block b of the MCU -> its component's DC and AC slots
+        const int c = tid < f.nluma ? 0 : min(tid - f.nluma + 1, 2);
+        bsel[2 * tid] = f.packed[OFF_SEL + 4 * c + 1] & 3;
+        bsel[2 * tid + 1] = f.packed[OFF_SEL + 4 * c + 2] & 3;
+    }
+    const unsigned int ent_off = (unsigned int)OFF_SEG + 16u * (unsigned int)f.nseg;
+    s.words = reinterpret_cast<const unsigned int*>(f.packed + ent_off);
+    s.nwords = (packed_len - ent_off) >> 2;
+    s.tab = tab;
+    s.bsel = bsel;
+    s.bpm = f.bpm;
+}
+
+// One restart segment by one workgroup: pass 1, the rounds, the scan, the writing pass, the DC prefix (the schedule at the top).
+// Every check is against f, the segment's own file.  Ends behind a barrier: wsum and the tables are free again.
+__device__ inline void jpeg_dec_huff_segment(const jpeg_dec::Stream& s, const JpegDecHuffFile& f, int seg, unsigned int* wsum,
+                                             unsigned int& status) {
+    using namespace jpeg_dec;
+    constexpr unsigned int S = JPEG_DEC_SUBSEQ_BITS;
+    constexpr int T = JPEG_DEC_THREADS;
+    const int tid = threadIdx.x;
+    const int bpm = f.bpm;
+    unsigned int unused = 0;
+    const uint4 sg = *reinterpret_cast<const uint4*>(f.packed + OFF_SEG + 16 * (size_t)seg);
+    const unsigned int p0 = sg.x, seg_end = sg.x + sg.y, sub0 = sg.z;
+    const unsigned int n = (sg.y + S - 1) / S;
+    const unsigned int nblk = sg.w * (unsigned int)bpm;
+    const unsigned int blk_base = (unsigned int)seg * (unsigned int)f.restart * (unsigned int)bpm;
+    // the segment table is data: what it says must fit the workspace (uniform over the workgroup)
+    if (seg_end < p0 || (unsigned long long)sub0 + n > (unsigned long long)f.nsub_total || (seg_end >> 5) > s.nwords ||
+        (f.restart ? sg.w > (unsigned int)f.restart : seg != 0) ||
+        (unsigned long long)seg * (unsigned int)f.restart + sg.w > (unsigned long long)f.nmcu) {
+        status |= ST_LAYOUT;
+        return;
+    }
+    uint4* A = f.state + 2 * (size_t)sub0;
+    uint4* B = A + n;
+    auto sub_end = [&](unsigned int i) { return min(p0 + (i + 1) * S, seg_end); };
+    for (unsigned int i = tid; i < n; i += T) {           // pass 1
+        unsigned int p = p0 + i * S, bz = 0;
+        const unsigned int cnt = step<false>(s, p, bz, sub_end(i), seg_end, nullptr, 0, 0, unused);
+        A[i] = make_uint4(p, bz, cnt, 1);
+    }
+    __syncthreads();
+    int r = 0, any = 1;
+    while (any && r < (int)n) {                           // rounds
+        ++r;
+        int mine = 0;
+        for (unsigned int i = tid; i < n; i += T) {
+            uint4 e = A[i];
+            e.w = 0;
+            if (i > 0) {
+                const uint4 prev = A[i - 1];
+                if (prev.w) {
+                    unsigned int p = prev.x, bz = prev.y;
+                    const unsigned int cnt = step<false>(s, p, bz, sub_end(i), seg_end, nullptr, 0, 0, unused);
+                    e = make_uint4(p, bz, cnt, (p != e.x || bz != e.y) ? 1u : 0u);
+                }
+            }
+            B[i] = e;
+            mine |= (int)e.w;
+        }
+        any = __syncthreads_or(mine);
+        uint4* t = A;
+        A = B;
+        B = t;
+    }
+    if (any) status |= ST_ROUNDS;
+    if (tid == 0) f.rounds[seg] = r;
+    // first block of every subsequence: exclusive scan of the counts, 256 at a time with a carry
+    unsigned int carry = 0;
+    for (unsigned int base = 0; base < n; base += T) {
+        const unsigned int i = base + tid;
+        const unsigned int v = i < n ? A[i].z : 0;
+        unsigned int total;
+        const unsigned int ex = jpeg_enc::group_scan<T / 64>(v, wsum, total);
+        if (i < n) f.first[sub0 + i] = carry + ex;
+        carry += total;
+    }
+    if (carry != nblk) status |= ST_BLOCK_TOTAL;
+    // the writing pass, from the true states
+    for (unsigned int i = tid; i < n; i += T) {
+        unsigned int p = i ? A[i - 1].x : p0, bz = i ? A[i - 1].y : 0;
+        step<true>(s, p, bz, sub_end(i), seg_end, f.coef + (size_t)blk_base * 64, f.first[sub0 + i], nblk, status);
+    }
+    __syncthreads();
+    // DC differences -> values: per component, the blocks of the segment in scan order
+    const int ncomp = bpm == 1 ? 1 : 3;
+    for (int c = 0; c < ncomp; ++c) {
+        const unsigned int per = c == 0 ? (unsigned int)f.nluma : 1u, off = c == 0 ? 0u : (unsigned int)f.nluma + c - 1;
+        const unsigned int count = sg.w * per;
+        unsigned int acc = 0;
+        for (unsigned int base = 0; base < count; base += T) {
+            const unsigned int j = base + tid;
+            short* dc = f.coef + ((size_t)blk_base + (size_t)(j < count ? j / per : 0) * bpm + off + j % per) * 64;
+            const unsigned int v = j < count ? (unsigned int)(int)*dc : 0;
+            unsigned int total;
+            const unsigned int ex = jpeg_enc::group_scan<T / 64>(v, wsum, total);
+            if (j < count) *dc = (short)(acc + ex + v);
+            acc += total;
+        }
+    }
+    __syncthreads();                                      // the next segment reuses wsum
+}
+
 // grid: min(segments, a cap); workgroup w takes segments w, w + gridDim.x, ...
 __global__ void __launch_bounds__(JPEG_DEC_THREADS) jpeg_dec_huff_kernel(const unsigned char* __restrict__ packed, unsigned int packed_len,
                                                                          int nseg, int nsub_total, int nmcu, int bpm, int nluma, int restart,
@@ -493,121 +800,63 @@ __global__ void __launch_bounds__(JPEG_DEC_THREADS) jpeg_dec_huff_kernel(const u
                                                                          unsigned int* __restrict__ first, int* __restrict__ rounds,
                                                                          int* __restrict__ status_out) {
     using namespace jpeg_dec;
-    constexpr unsigned int S = JPEG_DEC_SUBSEQ_BITS;
-    constexpr int T = JPEG_DEC_THREADS;
     __shared__ HuffTable tab[4];
     __shared__ unsigned char bsel[16];
-    __shared__ unsigned int wsum[T / 64];
-    const int tid = threadIdx.x;
-    {
-        const unsigned int* src = reinterpret_cast<const unsigned int*>(packed + OFF_HUFF);
-        unsigned int* dst = reinterpret_cast<unsigned int*>(tab);
-        for (int i = tid; i < (int)(4 * sizeof(HuffTable) / 4); i += T) dst[i] = src[i];
-        if (tid < 8) {                                    // block b of the MCU -> its component's DC and AC slots
-            const int c = tid < nluma ? 0 : min(tid - nluma + 1, 2);
-            bsel[2 * tid] = packed[OFF_SEL + 4 * c + 1] & 3;
-            bsel[2 * tid + 1] = packed[OFF_SEL + 4 * c + 2] & 3;
-        }
-    }
-    __syncthreads();
-    const unsigned int ent_off = (unsigned int)OFF_SEG + 16u * (unsigned int)nseg;
+    __shared__ unsigned int wsum[JPEG_DEC_THREADS / 64];
+    const JpegDecHuffFile f = {packed, nseg, nsub_total, nmcu, bpm, nluma, restart, coef, state, first, rounds};
     Stream s;
-    s.words = reinterpret_cast<const unsigned int*>(packed + ent_off);
-    s.nwords = (packed_len - ent_off) >> 2;
-    s.tab = tab;
-    s.bsel = bsel;
-    s.bpm = bpm;
-    unsigned int status = 0, unused = 0;
-
-    for (int seg = blockIdx.x; seg < nseg; seg += gridDim.x) {
-        const uint4 sg = *reinterpret_cast<const uint4*>(packed + OFF_SEG + 16 * (size_t)seg);
-        const unsigned int p0 = sg.x, seg_end = sg.x + sg.y, sub0 = sg.z;
-        const unsigned int n = (sg.y + S - 1) / S;
-        const unsigned int nblk = sg.w * (unsigned int)bpm;
-        const unsigned int blk_base = (unsigned int)seg * (unsigned int)restart * (unsigned int)bpm;
-        // the segment table is data: what it says must fit the workspace (uniform over the workgroup)
-        if (seg_end < p0 || (unsigned long long)sub0 + n > (unsigned long long)nsub_total || (seg_end >> 5) > s.nwords ||
-            (restart ? sg.w > (unsigned int)restart : seg != 0) ||
-            (unsigned long long)seg * (unsigned int)restart + sg.w > (unsigned long long)nmcu) {
-            status |= ST_LAYOUT;
-            continue;
-        }
-        uint4* A = state + 2 * (size_t)sub0;
-        uint4* B = A + n;
-        auto sub_end = [&](unsigned int i) { return min(p0 + (i + 1) * S, seg_end); };
-        for (unsigned int i = tid; i < n; i += T) {       // pass 1
-            unsigned int p = p0 + i * S, bz = 0;
-            const unsigned int cnt = step<false>(s, p, bz, sub_end(i), seg_end, nullptr, 0, 0, unused);
-            A[i] = make_uint4(p, bz, cnt, 1);
-        }
-        __syncthreads();
-        int r = 0, any = 1;
-        while (any && r < (int)n) {                       // rounds
-            ++r;
-            int mine = 0;
-            for (unsigned int i = tid; i < n; i += T) {
-                uint4 e = A[i];
-                e.w = 0;
-                if (i > 0) {
-                    const uint4 prev = A[i - 1];
-                    if (prev.w) {
-                        unsigned int p = prev.x, bz = prev.y;
-                        const unsigned int cnt = step<false>(s, p, bz, sub_end(i), seg_end, nullptr, 0, 0, unused);
-                        e = make_uint4(p, bz, cnt, (p != e.x || bz != e.y) ? 1u : 0u);
-                    }
-                }
-                B[i] = e;
-                mine |= (int)e.w;
-            }
-            any = __syncthreads_or(mine);
-            uint4* t = A;
-            A = B;
-            B = t;
-        }
-        if (any) status |= ST_ROUNDS;
-        if (tid == 0) rounds[seg] = r;
-        // first block of every subsequence: exclusive scan of the counts, 256 at a time with a carry
-        unsigned int carry = 0;
-        for (unsigned int base = 0; base < n; base += T) {
-            const unsigned int i = base + tid;
-            const unsigned int v = i < n ? A[i].z : 0;
-            unsigned int total;
-            const unsigned int ex = jpeg_enc::group_scan<T / 64>(v, wsum, total);
-            if (i < n) first[sub0 + i] = carry + ex;
-            carry += total;
-        }
-        if (carry != nblk) status |= ST_BLOCK_TOTAL;
-        // the writing pass, from the true states
-        for (unsigned int i = tid; i < n; i += T) {
-            unsigned int p = i ? A[i - 1].x : p0, bz = i ? A[i - 1].y : 0;
-            step<true>(s, p, bz, sub_end(i), seg_end, coef + (size_t)blk_base * 64, first[sub0 + i], nblk, status);
-        }
-        __syncthreads();
-        // DC differences -> values: per component, the blocks of the segment in scan order
-        const int ncomp = bpm == 1 ? 1 : 3;
-        for (int c = 0; c < ncomp; ++c) {
-            const unsigned int per = c == 0 ? (unsigned int)nluma : 1u, off = c == 0 ? 0u : (unsigned int)nluma + c - 1;
-            const unsigned int count = sg.w * per;
-            unsigned int acc = 0;
-            for (unsigned int base = 0; base < count; base += T) {
-                const unsigned int j = base + tid;
-                short* dc = coef + ((size_t)blk_base + (size_t)(j < count ? j / per : 0) * bpm + off + j % per) * 64;
-                const unsigned int v = j < count ? (unsigned int)(int)*dc : 0;
-                unsigned int total;
-                const unsigned int ex = jpeg_enc::group_scan<T / 64>(v, wsum, total);
-                if (j < count) *dc = (short)(acc + ex + v);
-                acc += total;
-            }
-        }
-        __syncthreads();                                  // the next segment reuses wsum
-    }
+    jpeg_dec_huff_load(f, packed_len, tab, bsel, s);
+    __syncthreads();
+    unsigned int status = 0;
+    for (int seg = blockIdx.x; seg < nseg; seg += gridDim.x) jpeg_dec_huff_segment(s, f, seg, wsum, status);
     if (status) atomicOr(status_out, (int)status);
 }
 
-// grid: ceil(blocks / 32); eight lanes per block, 32 blocks per workgroup.  planes: Y (yh x yw), then Cb, Cr (ch x cw each).
-__global__ void __launch_bounds__(256) jpeg_dec_idct_kernel(const short* __restrict__ coef, const unsigned char* __restrict__ packed,
-                                                            int nblk, int bpm, int hs, int vs, int mcus_x,
-                                                            unsigned char* __restrict__ planes, int yw, int yh, int cw, int ch) {
+// The Huffman stage of a batch (the table: "several files per call" above).  grid: min(items, a cap); workgroup w takes items w,
+// w + gridDim.x, ... of the table, each one restart segment of one file.  Where an item's file is not the one before it, the
+// workgroup ORs what it found into the old file's status word and reloads the tables: a barrier in front, so that no wave still
+// decodes with the old ones (a refused segment returns without one), and a barrier behind.  Everything here is uniform over the
+// workgroup.  A file index outside the table (the table is the host's, not the file's) skips the item.
+__global__ void __launch_bounds__(JPEG_DEC_THREADS) jpeg_dec_huff_batch_kernel(const unsigned char* __restrict__ buf,
+                                                                               unsigned char* __restrict__ ws, int* __restrict__ status_out) {
+    using namespace jpeg_dec;
+    __shared__ HuffTable tab[4];
+    __shared__ unsigned char bsel[16];
+    __shared__ unsigned int wsum[JPEG_DEC_THREADS / 64];
+    const BatchHeader* hd = reinterpret_cast<const BatchHeader*>(buf);
+    const BatchFile* files = reinterpret_cast<const BatchFile*>(buf + sizeof(BatchHeader));
+    const BatchItem* items = reinterpret_cast<const BatchItem*>(buf + hd->off_items);
+    const unsigned int nfiles = hd->n, nitems = hd->nitems;
+    Stream s = {};
+    unsigned int status = 0, cur = 0xffffffffu;
+    for (unsigned int it = blockIdx.x; it < nitems; it += gridDim.x) {
+        const BatchItem item = items[it];
+        if (item.file >= nfiles) continue;
+        const BatchFile& d = files[item.file];            // read again for every item: less to keep across the segment's work
+        const JpegDecHuffFile f = {buf + d.packed_off, d.nseg, d.nsub, d.nmcu, d.bpm, d.nluma, d.restart,
+                                   reinterpret_cast<short*>(ws + d.coef_off), reinterpret_cast<uint4*>(ws + d.state_off),
+                                   reinterpret_cast<unsigned int*>(ws + d.first_off), reinterpret_cast<int*>(ws + d.rounds_off)};
+        if (item.file != cur) {
+            if (status) atomicOr(status_out + cur, (int)status);
+            status = 0;
+            cur = item.file;
+            __syncthreads();
+            jpeg_dec_huff_load(f, d.packed_len, tab, bsel, s);
+            __syncthreads();
+        }
+        if (item.seg >= (unsigned int)f.nseg) {
+            status |= ST_LAYOUT;
+            continue;
+        }
+        jpeg_dec_huff_segment(s, f, (int)item.seg, wsum, status);
+    }
+    if (status) atomicOr(status_out + cur, (int)status);
+}
+
+// The 32 blocks from block 32 x wg on of one file, by one workgroup: eight lanes per block.  planes: Y (yh x yw), then Cb, Cr
+// (ch x cw each).
+__device__ inline void jpeg_dec_idct_blocks(const short* __restrict__ coef, const unsigned char* __restrict__ packed, int wg, int nblk, int bpm,
+                                            int hs, int vs, int mcus_x, unsigned char* __restrict__ planes, int yw, int yh, int cw, int ch) {
     using namespace jpeg;
     __shared__ int blk[32][8][9];
     __shared__ unsigned char q[4][64];
@@ -616,7 +865,7 @@ __global__ void __launch_bounds__(256) jpeg_dec_idct_kernel(const short* __restr
     if (threadIdx.x < 3) qsel[threadIdx.x] = packed[jpeg_dec::OFF_SEL + 4 * threadIdx.x] & 3;
     __syncthreads();
     const int k = threadIdx.x >> 3, i8 = threadIdx.x & 7;
-    const int g = blockIdx.x * 32 + k;
+    const int g = wg * 32 + k;
     const bool valid = g < nblk;                          // every thread reaches the barrier
     const int nluma = hs * vs;
     const int mcu = valid ? g / bpm : 0, b = valid ? g % bpm : 0;
@@ -650,11 +899,42 @@ __global__ void __launch_bounds__(256) jpeg_dec_idct_kernel(const short* __restr
     }
 }
 
-// one thread per pixel of the crop.  W, H: the image; out: (h, w, 3)
-__global__ void __launch_bounds__(256) jpeg_dec_colour_kernel(const unsigned char* __restrict__ planes, unsigned char* __restrict__ out,
-                                                              int W, int H, int ncomp, int hs, int vs, int yw, int yh, int cw, int ch,
-                                                              int x0, int y0, int w, int h, int bgr) {
-    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+// grid: ceil(blocks / 32)
+__global__ void __launch_bounds__(256) jpeg_dec_idct_kernel(const short* __restrict__ coef, const unsigned char* __restrict__ packed,
+                                                            int nblk, int bpm, int hs, int vs, int mcus_x,
+                                                            unsigned char* __restrict__ planes, int yw, int yh, int cw, int ch) {
+    jpeg_dec_idct_blocks(coef, packed, (int)blockIdx.x, nblk, bpm, hs, vs, mcus_x, planes, yw, yh, cw, ch);
+}
+
+// The file of workgroup wg: the k with prefix[k] <= wg < prefix[k + 1] (prefix: n + 1 ascending words, prefix[0] = 0, every file
+// has at least one workgroup).  Uniform over the workgroup; the result is below n whatever the table holds.
+__device__ inline unsigned int jpeg_dec_batch_file(const unsigned int* __restrict__ prefix, unsigned int n, unsigned int wg) {
+    unsigned int lo = 0, hi = n;                          // prefix[lo] <= wg < prefix[hi]
+    while (hi - lo > 1) {
+        const unsigned int mid = (lo + hi) >> 1;
+        if (prefix[mid] <= wg) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// The IDCT stage of a batch.  grid: the table's idct_wgs
+__global__ void __launch_bounds__(256) jpeg_dec_idct_batch_kernel(const unsigned char* __restrict__ buf, unsigned char* __restrict__ ws) {
+    using namespace jpeg_dec;
+    const BatchHeader* hd = reinterpret_cast<const BatchHeader*>(buf);
+    const unsigned int* prefix = reinterpret_cast<const unsigned int*>(buf + hd->off_idct);
+    const unsigned int k = jpeg_dec_batch_file(prefix, hd->n, blockIdx.x);
+    const BatchFile& d = reinterpret_cast<const BatchFile*>(buf + sizeof(BatchHeader))[k];
+    const unsigned int wg = blockIdx.x - prefix[k];
+    if (wg >= ((unsigned int)d.nblk + 31u) / 32u) return; // uniform: a table that is not the plan's
+    const int mcus_y = d.nmcu / d.mcus_x;
+    jpeg_dec_idct_blocks(reinterpret_cast<const short*>(ws + d.coef_off), buf + d.packed_off, (int)wg, d.nblk, d.bpm, d.hs, d.vs, d.mcus_x,
+                         ws + d.planes_off, d.mcus_x * 8 * d.hs, mcus_y * 8 * d.vs, d.mcus_x * 8, mcus_y * 8);
+}
+
+// pixel t of the crop.  W, H: the image; out: (h, w, 3)
+__device__ inline void jpeg_dec_colour_pixel(const unsigned char* __restrict__ planes, unsigned char* __restrict__ out, long long t, int W, int H,
+                                             int ncomp, int hs, int vs, int yw, int yh, int cw, int ch, int x0, int y0, int w, int h, int bgr) {
     if (t >= (long long)w * h) return;
     const int oy = (int)(t / w), ox = (int)(t - (long long)oy * w);
     const int y = y0 + oy, x = x0 + ox;
@@ -694,6 +974,26 @@ __global__ void __launch_bounds__(256) jpeg_dec_colour_kernel(const unsigned cha
     o[0] = (unsigned char)(bgr ? bl : r);
     o[1] = (unsigned char)g;
     o[2] = (unsigned char)(bgr ? r : bl);
+}
+
+// one thread per pixel of the crop
+__global__ void __launch_bounds__(256) jpeg_dec_colour_kernel(const unsigned char* __restrict__ planes, unsigned char* __restrict__ out,
+                                                              int W, int H, int ncomp, int hs, int vs, int yw, int yh, int cw, int ch,
+                                                              int x0, int y0, int w, int h, int bgr) {
+    jpeg_dec_colour_pixel(planes, out, (long long)blockIdx.x * 256 + threadIdx.x, W, H, ncomp, hs, vs, yw, yh, cw, ch, x0, y0, w, h, bgr);
+}
+
+// The colour stage of a batch.  grid: the table's colour_wgs; every file writes its own crop at its own offset of out
+__global__ void __launch_bounds__(256) jpeg_dec_colour_batch_kernel(const unsigned char* __restrict__ buf, const unsigned char* __restrict__ ws,
+                                                                    unsigned char* __restrict__ out, int bgr) {
+    using namespace jpeg_dec;
+    const BatchHeader* hd = reinterpret_cast<const BatchHeader*>(buf);
+    const unsigned int* prefix = reinterpret_cast<const unsigned int*>(buf + hd->off_colour);
+    const unsigned int k = jpeg_dec_batch_file(prefix, hd->n, blockIdx.x);
+    const BatchFile& d = reinterpret_cast<const BatchFile*>(buf + sizeof(BatchHeader))[k];
+    const int mcus_y = d.nmcu / d.mcus_x;
+    jpeg_dec_colour_pixel(ws + d.planes_off, out + d.out_off, (long long)(blockIdx.x - prefix[k]) * 256 + threadIdx.x, d.W, d.H, d.ncomp, d.hs,
+                          d.vs, d.mcus_x * 8 * d.hs, mcus_y * 8 * d.vs, d.mcus_x * 8, mcus_y * 8, d.x0, d.y0, d.w, d.h, bgr);
 }
 #endif  // __HIPCC__
 #endif

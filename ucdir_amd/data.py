@@ -4,7 +4,8 @@ sorted file lists of dataroot.lq / dataroot.gt, RGB, scaled to [-1, 1] (data/uti
 loader ImagenetSRDataset (reference: data/LRHR_dataset.py:385-443); and the real-world SR loader RealESRGANDataset (reference:
 data/LRHR_dataset.py:668-807).  The three ImageNet loaders take ``decode_device``: "cpu" (the default) decodes the file with
 Pillow on the host and uploads the pixels; "gpu" uploads the file's bytes and decodes them with csrc/jpeg_decode.hip.h, the same
-pixels, falling back to Pillow per image for what that decoder does not take (``decode_fallbacks``)."""
+pixels, falling back to Pillow per image for what that decoder does not take (``decode_fallbacks``); ``prefetch(indices)`` then
+decodes a set of files through one batch call ahead of the items that use them."""
 import os
 
 import numpy as np
@@ -55,24 +56,63 @@ def _check_decode_device(v):
     return v
 
 
+def _region_of(data, region):
+    """The (left, top, width, height) crop ``region`` takes of the JPEG file ``data``, or None for the whole image.  Raises
+    JpegUnsupported for a file the decoder does not take and for an empty crop."""
+    from .metrics import JpegUnsupported, jpeg_info
+    info = jpeg_info(data)
+    crop = region(info["width"], info["height"])
+    if crop is not None and (crop[2] < 1 or crop[3] < 1):
+        raise JpegUnsupported(0, "the loader's crop of this image is empty")
+    return crop
+
+
 def decode_u8_device(ds, i, region, dev):
     """The ``decode_device = "gpu"`` half of the ImageNet loaders: read the bytes of image ``i`` of loader ``ds`` and decode them on
     ``dev`` (csrc/jpeg_decode.hip.h, byte for byte Pillow's convert("RGB")).  ``region(w, h)`` -> None for the whole image or the
     (left, top, width, height) crop the loader takes of a w x h image.  Returns (uint8 CUDA tensor, whether it is already cropped),
     or None for a file the decoder does not take (not a JPEG, progressive, CMYK, damaged, ...): the loader then decodes that image
-    with Pillow, and ``ds.decode_fallbacks`` gains (index, reason)."""
-    from .metrics import JpegUnsupported, jpeg_decode_device, jpeg_info
-    with open(ds.hr_path[i], "rb") as f:
-        data = f.read()
+    with Pillow, and ``ds.decode_fallbacks`` gains (index, reason).  An image that ``prefetch`` decoded is taken from there, once."""
+    from .metrics import JpegUnsupported, jpeg_decode_device
     try:
-        info = jpeg_info(data)
-        crop = region(info["width"], info["height"])
-        if crop is not None and (crop[2] < 1 or crop[3] < 1):
-            raise JpegUnsupported(0, "the loader's crop of this image is empty")
+        got = ds.prefetched.pop(i, None)                 # what prefetch left: (tensor, cropped) or the decoder's refusal
+        if isinstance(got, JpegUnsupported):
+            raise got
+        if got is not None and got[0].device == dev:
+            return got
+        with open(ds.hr_path[i], "rb") as f:
+            data = f.read()
+        crop = _region_of(data, region)
         return jpeg_decode_device(data, crop=crop, device=dev), crop is not None
     except JpegUnsupported as e:
         ds.decode_fallbacks.append((i, e.reason))
         return None
+
+
+def prefetch_u8_device(ds, indices, region, dev=None):
+    """The ``prefetch`` of the ImageNet loaders: with ``decode_device = "gpu"``, read the files of ``indices``, take each one's
+    ``region`` crop from its info and decode the whole set through ONE metrics.jpeg_decode_batch_device call on ``dev`` (default:
+    the current GPU).  The results wait in ``ds.prefetched`` until decode_u8_device asks for that index, which hands each out
+    once; a file the decoder refused waits there as its JpegUnsupported and takes the Pillow fallback then, so that
+    ``decode_fallbacks`` fills as it does without prefetch.  With "cpu" nothing happens."""
+    from .metrics import JpegUnsupported, jpeg_decode_batch_device
+    if ds.decode_device != "gpu":
+        return
+    dev = torch.device("cuda", torch.cuda.current_device()) if dev is None else torch.device(dev)
+    idx, datas, crops = [], [], []
+    for i in dict.fromkeys(int(i) for i in indices):
+        with open(ds.hr_path[i], "rb") as f:
+            data = f.read()
+        try:
+            crop = _region_of(data, region)
+        except JpegUnsupported as e:
+            ds.prefetched[i] = e
+            continue
+        idx.append(i)
+        datas.append(data)
+        crops.append(crop)
+    for i, crop, got in zip(idx, crops, jpeg_decode_batch_device(datas, crops, device=dev)):
+        ds.prefetched[i] = got if isinstance(got, JpegUnsupported) else (got, crop is not None)
 
 
 def _u8_to_unit(x):
@@ -119,6 +159,7 @@ class ImagenetJPGDataset:
         self.factor = list(data_args.get("factor") or [5, 5])
         self.decode_device = _check_decode_device(decode_device)
         self.decode_fallbacks = []                   # (index, reason) of every image "gpu" had to leave to Pillow
+        self.prefetched = {}                         # index -> what prefetch decoded and no item has asked for yet
 
     def __len__(self):
         return len(self.hr_path)
@@ -137,19 +178,24 @@ class ImagenetJPGDataset:
         img = img.crop((left, top, left + cw, top + ch))
         return np.array(img, dtype=np.uint8)             # a writable copy (torch.from_numpy of PIL's read-only view warns)
 
+    def region(self, w, h):
+        """The crop the decoder takes of a w x h image: load_u8's centred crop, or None (the whole image) below crop_size."""
+        cs = self.crop_size
+        if min(w, h) < cs:
+            return None
+        cw, ch = (cs, cs) if cs > 0 else (w // 16 * 16, h // 16 * 16)
+        return (w - cw) // 2, (h - ch) // 2, cw, ch
+
+    def prefetch(self, indices, dev=None):
+        """Decode the files of ``indices`` in one batch call ahead of their items (prefetch_u8_device)."""
+        prefetch_u8_device(self, indices, self.region, dev)
+
     def load_u8_device(self, i, dev):
         """load_u8 with the decode on the GPU -> the same (H, W, 3) uint8 image as a tensor on ``dev``.  The centred crop is taken
         inside the decoder; an image below crop_size is decoded whole and resized there first (Pillow's resize default, bicubic)."""
         from .metrics import resample_device
         cs = self.crop_size
-
-        def region(w, h):
-            if min(w, h) < cs:
-                return None
-            cw, ch = (cs, cs) if cs > 0 else (w // 16 * 16, h // 16 * 16)
-            return (w - cw) // 2, (h - ch) // 2, cw, ch
-
-        got = decode_u8_device(self, i, region, dev)
+        got = decode_u8_device(self, i, self.region, dev)
         if got is None:
             return torch.from_numpy(self.load_u8(i)).to(dev)
         img, cropped = got
@@ -204,6 +250,7 @@ class ImagenetSRDataset:
         self.last_lr64 = None
         self.decode_device = _check_decode_device(decode_device)
         self.decode_fallbacks = []                   # (index, reason) of every image "gpu" had to leave to Pillow
+        self.prefetched = {}                         # index -> what prefetch decoded and no item has asked for yet
 
     def __len__(self):
         return len(self.hr_path)
@@ -227,8 +274,16 @@ class ImagenetSRDataset:
 
     def load_u8_device(self, i, dev):
         """load_u8 with the decode on the GPU: the whole image, as degrade_u8 takes it."""
-        got = decode_u8_device(self, i, lambda w, h: None, dev)
+        got = decode_u8_device(self, i, self.region, dev)
         return torch.from_numpy(self.load_u8(i)).to(dev) if got is None else got[0]
+
+    def region(self, w, h):
+        """The decoder takes the whole image."""
+        return None
+
+    def prefetch(self, indices, dev=None):
+        """Decode the files of ``indices`` in one batch call ahead of their items (prefetch_u8_device)."""
+        prefetch_u8_device(self, indices, self.region, dev)
 
     def __getitem__(self, i):
         dev = torch.device("cuda", torch.cuda.current_device())
@@ -286,6 +341,7 @@ class RealESRGANDataset:
         self.kopt = load_settings(data_args.get("param") or "param")
         self.decode_device = _check_decode_device(decode_device)
         self.decode_fallbacks = []                   # (index, reason) of every image "gpu" had to leave to Pillow
+        self.prefetched = {}                         # index -> what prefetch decoded and no item has asked for yet
 
     def __len__(self):
         return len(self.hr_path)
@@ -298,12 +354,21 @@ class RealESRGANDataset:
         top, left = (img.shape[0] - cs) // 2, (img.shape[1] - cs) // 2
         return np.ascontiguousarray(img[top:top + cs, left:left + cs])
 
+    def region(self, w, h):
+        """The crop the decoder takes of a w x h image: the centred one where the image covers it, else None (the whole image)."""
+        cs = self.crop_size
+        return ((w - cs) // 2, (h - cs) // 2, cs, cs) if w >= cs and h >= cs else None
+
+    def prefetch(self, indices, dev=None):
+        """Decode the files of ``indices`` in one batch call ahead of their items (prefetch_u8_device)."""
+        prefetch_u8_device(self, indices, self.region, dev)
+
     def load_u8_device(self, i, dev):
         """load_u8 with the decode on the GPU -> the same (crop_size, crop_size, 3) uint8 image as a tensor on ``dev``.  An image
         that covers the crop is cropped inside the decoder; a smaller one is decoded whole, then padded and cropped there by
         gathering the rows and columns reflect101_index names."""
         cs = self.crop_size
-        got = decode_u8_device(self, i, lambda w, h: ((w - cs) // 2, (h - cs) // 2, cs, cs) if w >= cs and h >= cs else None, dev)
+        got = decode_u8_device(self, i, self.region, dev)
         if got is None:
             return torch.from_numpy(self.load_u8(i)).to(dev)
         img, cropped = got

@@ -66,6 +66,10 @@ _SIGS = {
                                     c_void_p, c_void_p]),
     "ucdir_jpeg_decode_profile": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
                                             c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ucdir_jpeg_decode_batch_plan": (c_int64, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "ucdir_jpeg_decode_batch": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
+    "ucdir_jpeg_decode_batch_profile": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p,
+                                                  c_void_p, c_void_p, c_void_p]),
     "ucdir_resample_coeffs": (c_int32, [c_int32, c_int32, c_int32, c_void_p, c_void_p, POINTER(c_int32)]),
     "ucdir_resample_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32]),
     "ucdir_resample": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),

@@ -230,6 +230,21 @@ def jpeg_info(data):
     return dict(zip(JPEG_INFO_FIELDS, info.tolist()))
 
 
+def _jpeg_crop(crop, info, who):
+    """``crop`` (None: the whole image) as four ints inside the image of ``info``, or a ValueError in ``who``'s name."""
+    W, H = int(info[0]), int(info[1])
+    if crop is None:
+        return 0, 0, W, H
+    try:
+        x0, y0, w, h = crop
+        ok = all(not isinstance(v, bool) and int(v) == v for v in crop)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok or w < 1 or h < 1 or x0 < 0 or y0 < 0 or x0 + w > W or y0 + h > H:
+        raise ValueError(f"{who}: crop (left, top, width, height) = {crop!r} does not lie inside the {W} x {H} image")
+    return int(x0), int(y0), int(w), int(h)
+
+
 def jpeg_decode_device(data, crop=None, bgr=False, device=None):
     """Decode the bytes of a baseline JPEG file on the GPU (csrc/jpeg_decode.hip.h): byte for byte what Pillow's
     Image.open(...).convert("RGB") gives.  ``data``: bytes; ``crop``: None or (left, top, width, height) inside the image;
@@ -244,16 +259,7 @@ def jpeg_decode_device(data, crop=None, bgr=False, device=None):
     if code != 0:
         raise JpegUnsupported(code, JPEG_INFO_REASONS.get(code, "unknown"))
     L = lib.load()
-    W, H = int(info[0]), int(info[1])
-    if crop is None:
-        crop = (0, 0, W, H)
-    try:
-        x0, y0, w, h = crop
-        ok = all(not isinstance(v, bool) and int(v) == v for v in crop)
-    except (TypeError, ValueError):
-        ok = False
-    if not ok or w < 1 or h < 1 or x0 < 0 or y0 < 0 or x0 + w > W or y0 + h > H:
-        raise ValueError(f"jpeg_decode_device: crop (left, top, width, height) = {crop!r} does not lie inside the {W} x {H} image")
+    x0, y0, w, h = _jpeg_crop(crop, info, "jpeg_decode_device")
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     if dev.type != "cuda":
         raise ValueError(f"jpeg_decode_device decodes on a GPU, got device {dev}")
@@ -271,8 +277,78 @@ def jpeg_decode_device(data, crop=None, bgr=False, device=None):
                                       1 if bgr else 0, _ptr(ws), _ptr(status), _stream_ptr(dev)))
         st = int(status.item())                        # the synchronisation
     if st != 0:
-        raise JpegUnsupported(st, "damaged entropy data: " + ", ".join(v for k, v in JPEG_STATUS_BITS.items() if st & k), device_status=True)
+        raise JpegUnsupported(st, _damage_reason(st), device_status=True)
     return out
+
+
+def _damage_reason(st):
+    return "damaged entropy data: " + ", ".join(v for k, v in JPEG_STATUS_BITS.items() if st & k)
+
+
+def jpeg_decode_batch_device(datas, crops=None, bgr=False, device=None):
+    """Decode the bytes of several baseline JPEG files on the GPU in one call (csrc/jpeg_decode.hip.h, "several files per call").
+    ``datas``: a sequence of bytes; ``crops``: None, or per file None or (left, top, width, height); ``bgr`` and ``device`` as
+    jpeg_decode_device takes them -> a list: entry k is the (h, w, 3) uint8 tensor jpeg_decode_device(datas[k], crops[k]) returns,
+    or, for a file that decoder does not take, the JpegUnsupported it would raise, as an instance in the list (a refusal by the
+    host framing: the info code; damage the kernels found: that file's status bits, device_status=True); the other files are not
+    affected.  One parse and pack per file on the host, one upload, one batch call, and one wait for all status words.  The
+    tensors are views into ONE allocation that lives as long as any of them: clone what is to outlive the rest cheaply.
+    Raises ValueError, naming the file's position, for an entry that is not bytes or a crop outside its image."""
+    import torch
+    from . import lib
+    from .ucdir import _ptr, _stream_ptr
+    datas = list(datas)
+    crops = [None] * len(datas) if crops is None else list(crops)
+    if len(crops) != len(datas):
+        raise ValueError(f"jpeg_decode_batch_device: {len(crops)} crops for {len(datas)} files")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev.type != "cuda":
+        raise ValueError(f"jpeg_decode_batch_device decodes on a GPU, got device {dev}")
+    res, take = [None] * len(datas), []                   # take: (position, info words, file bytes as an array, crop)
+    for k, (data, crop) in enumerate(zip(datas, crops)):
+        try:
+            code, info, src = _jpeg_info_words(data)
+        except ValueError as e:
+            raise ValueError(f"jpeg_decode_batch_device: file {k}: {e}") from None
+        if code != 0:
+            res[k] = JpegUnsupported(code, JPEG_INFO_REASONS.get(code, "unknown"))
+            continue
+        take.append((k, info, src, _jpeg_crop(crop, info, f"jpeg_decode_batch_device: file {k}")))
+    if not take:
+        return res
+    L = lib.load()
+    n = len(take)
+    infos = np.ascontiguousarray(np.stack([t[1] for t in take]))
+    crop_arr = np.array([t[3] for t in take], np.int32)
+    ws_bytes = np.zeros(1, np.int64)
+    table = L.ucdir_jpeg_decode_batch_plan(n, infos.ctypes.data, None, None, None, None, 0, ws_bytes.ctypes.data)
+    if table < 0:
+        lib.check(1)
+    packed_off = table + np.concatenate([[0], np.cumsum((infos[:, 9].astype(np.int64) + 15) // 16 * 16)])
+    npix = crop_arr[:, 2].astype(np.int64) * crop_arr[:, 3]
+    out_off = np.concatenate([[0], np.cumsum(3 * npix)]).astype(np.int64)
+    packed_off = packed_off.astype(np.int64)
+    buf = torch.zeros(int(packed_off[-1]), dtype=torch.uint8)
+    for j, (_, info, src, _) in enumerate(take):
+        if L.ucdir_jpeg_decode_pack(src.ctypes.data, len(src), buf.data_ptr() + int(packed_off[j]), int(info[9])) != int(info[9]):
+            raise lib.UcdirError("ucdir_jpeg_decode_pack disagrees with ucdir_jpeg_decode_info")
+    if L.ucdir_jpeg_decode_batch_plan(n, infos.ctypes.data, crop_arr.ctypes.data, packed_off.ctypes.data, out_off.ctypes.data,
+                                      buf.data_ptr(), buf.numel(), None) != table:
+        lib.check(1)
+    with torch.cuda.device(dev):
+        buf_dev = buf.to(dev)                             # the one upload
+        ws = torch.empty(int(ws_bytes[0]), dtype=torch.uint8, device=dev)
+        out = torch.empty(int(out_off[-1]), dtype=torch.uint8, device=dev)
+        status = torch.empty(n, dtype=torch.int32, device=dev)
+        lib.check(L.ucdir_jpeg_decode_batch(_ptr(buf_dev), buf.data_ptr(), buf.numel(), _ptr(out), out.numel(), 1 if bgr else 0, _ptr(ws),
+                                            ws.numel(), _ptr(status), _stream_ptr(dev)))
+        st = status.cpu().tolist()                        # the one synchronisation
+    for j, (k, _, _, (_, _, w, h)) in enumerate(take):
+        if st[j] != 0:
+            res[k] = JpegUnsupported(st[j], _damage_reason(st[j]), device_status=True)
+        else:
+            res[k] = out[int(out_off[j]):int(out_off[j + 1])].view(h, w, 3)
+    return res
 
 
 def load_rgb_u8(path, decode_device="cpu", fallbacks=None):
