@@ -223,6 +223,7 @@ int32_t ucdir_jpeg_encode(const uint8_t* in, uint8_t* out, int32_t* lengths, int
  *       [y0, y0 + h) x [x0, x0 + w), which must lie inside the image; bgr != 0 swaps channels 0 and 2; status_dev: one int32 on
  *       the device, 0 or the OR of damage bits (1 category out of range, 2 a code outside the table, 4 a coefficient outside
  *       its block or segment, 8 wrong block total, 16 no fixed point, 32 bad segment table), in which case out is undefined.
+ *       Fewer than 8 padding bits of any value behind a segment's last MCU are accepted; spare whole bytes there are damage.
  *       One image per call; asynchronous on `stream`, no allocation.
  *   ucdir_jpeg_decode_profile   the same decode for measurements and tests: records an event in front of and behind every stage,
  *       WAITS for the stream, and fills stage_ms_host (4 floats: the memsets, the Huffman, the IDCT and the colour stage, in ms) and

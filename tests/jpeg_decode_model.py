@@ -306,6 +306,8 @@ class Decoder:
             length[~found] = 16
             self.lut[s] = ((found.astype(np.int64) << 16) | (length << 8) | sym).tolist()
         self.tabs = [(self.lut[int(P["sel"][4 * c + 1])], self.lut[int(P["sel"][4 * c + 2])]) for c in self.comp]
+        self.max_code = [0, 0]                  # the longest DC and AC code a writing pass has met
+        self.symbols = None                     # a list: gains (first bit, last bit + 1) of every symbol of a writing pass
 
     def step(self, p, b, z, end, seg_end, write=None):
         """f: whole symbols from (p, b, z) until p >= end -> (p, b, z, blocks completed).  ``write``: (coef rows of the segment,
@@ -321,6 +323,9 @@ class Decoder:
             if left < 8 and (top >> (32 - left)) == (1 << left) - 1:
                 p = seg_end
                 break
+            if write is not None and z == 0 and left < 8 and blk0 + done == nblk:
+                p = seg_end                             # padding that is not 1-bits, behind the segment's last block
+                break
             e = tabs[b][1 if z else 0][top >> 16]
             ln, sym = (e >> 8) & 255, e & 255
             size = sym & 15
@@ -328,8 +333,13 @@ class Decoder:
             value = v - (1 << size) + 1 if size and v < (1 << (size - 1)) else v
             p += ln + size
             last = False
-            if write is not None and not e >> 16:
-                status[0] |= ST_NO_CODE
+            if write is not None:
+                k = 1 if z else 0
+                self.max_code[k] = max(self.max_code[k], ln)
+                if self.symbols is not None:
+                    self.symbols.append((p - ln - size, p))
+                if not e >> 16:
+                    status[0] |= ST_NO_CODE
             if z == 0:
                 if write is not None:
                     if sym > 11:
@@ -355,6 +365,8 @@ class Decoder:
                         status[0] |= ST_WRITE
                 z += 1
             if last or z >= 64:
+                if write is not None and blk0 + done >= nblk:
+                    status[0] |= ST_BLOCK_TOTAL         # a whole block more than the segment has
                 done += 1
                 if write is not None:
                     ends.append(p)
@@ -387,7 +399,7 @@ class Decoder:
             for i in range(n):
                 p, b, z, d = self.step(p, b, z, min(p0 + (i + 1) * S, seg_end), seg_end, (coef, done, status, []))
                 done += d
-            if done != nblk:
+            if done < nblk:
                 status[0] |= ST_BLOCK_TOTAL
             self.dc_sums(coef, nblk)
             out += coef
@@ -396,9 +408,13 @@ class Decoder:
     def fixed_point(self):
         """The subsequence schedule of jpeg_dec_huff_kernel -> (coefficients, status, stats).  stats: rounds (the most over the
         segments, the last round that changes nothing included), decodes (subsequence decodes of pass 1 and the rounds),
-        subsequences (the most in one segment), max_blocks_in_subsequence, max_block_bits (the longest block), last_segment_mcus."""
+        subsequences (the most in one segment), max_blocks_in_subsequence, max_block_bits (the longest block), last_segment_mcus;
+        per segment: segment_rounds, segment_subsequences, segment_bytes (unstuffed); max_dc_code and max_ac_code (the longest
+        code of either class the writing pass met); blocks_past_the_last (blocks the passes counted out of padding bits)."""
         out, status = [], [0]
-        st = dict(rounds=0, decodes=0, subsequences=0, max_blocks_in_subsequence=0, max_block_bits=0, total=0, last_segment_mcus=0)
+        st = dict(rounds=0, decodes=0, subsequences=0, max_blocks_in_subsequence=0, max_block_bits=0, total=0, last_segment_mcus=0,
+                  segment_rounds=[], segment_subsequences=[], segment_bytes=[], blocks_past_the_last=0)
+        self.max_code = [0, 0]
         for p0, seg_end, n, nblk, _ in self.segments():
             end = [min(p0 + (i + 1) * S, seg_end) for i in range(n)]
             A = [self.step(p0 + i * S, 0, 0, end[i], seg_end) + (1,) for i in range(n)]
@@ -424,7 +440,7 @@ class Decoder:
                 start = (p0, 0, 0) if i == 0 else A[i - 1][:3]
                 self.step(*start, end[i], seg_end, (coef, first, status, ends))
                 first += A[i][3]
-            if first != nblk:
+            if first < nblk:
                 status[0] |= ST_BLOCK_TOTAL
             self.dc_sums(coef, nblk)
             out += coef
@@ -435,6 +451,11 @@ class Decoder:
             st["max_blocks_in_subsequence"] = max([st["max_blocks_in_subsequence"]] + counts)
             st["max_block_bits"] = max([st["max_block_bits"]] + [b - a for a, b in zip(ends, ends[1:])])
             st["last_segment_mcus"] = nblk // self.bpm
+            st["segment_rounds"].append(r)
+            st["segment_subsequences"].append(n)
+            st["segment_bytes"].append((seg_end - p0) // 8)
+            st["blocks_past_the_last"] += max(first - nblk, 0)
+        st["max_dc_code"], st["max_ac_code"] = self.max_code
         return np.array(out, np.int64).reshape(-1, 64), status[0], st
 
 

@@ -124,7 +124,7 @@ static void schedule_segment(const Stream& s, const HuffFile& f, int seg, uint32
         f.first[sub0 + i] = carry;
         carry += A[i].cnt;
     }
-    if (carry != nblk) status |= ST_BLOCK_TOTAL;
+    if (carry < nblk) status |= ST_BLOCK_TOTAL;          // above: the writing pass tells padding from damage
     for (uint32_t i = 0; i < n; ++i) {
         uint32_t p = i ? A[i - 1].p : p0, bz = i ? A[i - 1].bz : 0;
         step<true>(s, p, bz, sub_end(i), seg_end, coef, f.first[sub0 + i], nblk, status);
@@ -169,7 +169,7 @@ static Result run_schedule(const std::vector<uint8_t>& packed, const int32_t* in
         uint32_t p = p0, bz = 0, done = 0;
         for (uint32_t i = 0; i < n; ++i)
             done += step<true>(s, p, bz, std::min(p0 + (i + 1) * S, seg_end), seg_end, coef, done, nblk, R.status);
-        if (done != nblk) R.status |= ST_BLOCK_TOTAL;
+        if (done < nblk) R.status |= ST_BLOCK_TOTAL;
         dc_sums(info, blk_base, sg[3], R.coef);
     }
     R.rounds = *std::max_element(rounds.begin(), rounds.end());

@@ -35,8 +35,8 @@
 //           true.  The true prefix grows by at least one subsequence per round, hence the bound; the worst case costs about one
 //           serial decode.  Every f also counts the blocks it completes, so at the fixed point cnt[i] is the true count of
 //           subsequence i: an exclusive scan (workgroup scan with a carry) gives every subsequence its first block, and one more
-//           decode writes every coefficient once, as int16 at (block, natural index), the DC as its difference.  A wrong block
-//           total sets the status.  Then the DC differences become values: a per-component prefix sum inside the segment.
+//           decode writes every coefficient once, as int16 at (block, natural index), the DC as its difference.  A block
+//           total below the segment's sets the status (above it: the writing pass sets it or not, see step()).  Then the DC differences become values: a per-component prefix sum inside the segment.
 //           No communication between workgroups, no atomics except the idempotent OR into the status word.
 //   idct    eight lanes per block: dequantise, jpeg::idct8 over columns, LDS, jpeg::idct8 over rows, jpeg::range_limit, one
 //           8-byte store per row into the component planes (padded to whole MCUs).
@@ -405,7 +405,11 @@ JPEG_DEC_HD inline int huff_extend(uint32_t v, int s) { return s && v < (1u << (
 // f: decode whole symbols from (p, bz = b << 8 | z) until p >= end; seg_end: the segment's last bit + 1 (fewer than 8 set bits
 // before it are the padding and end the decode).  Returns the blocks completed.  WRITE: the pass on true states - every
 // coefficient goes to coef[(blk0 + completed so far) * 64 + natural index] if that block is below nblk and z <= 63, and damage is
-// ORed into status.
+// ORed into status.  Padding of any other value (several encoders write 0-bits) looks like symbols: the passes without WRITE
+// decode and count them, which only disturbs the last subsequence's count and end state, and nobody reads either; the WRITE pass
+// ends without a status bit where a block past the segment's last would begin with fewer than 8 bits left, as libjpeg drops
+// what is left of the byte once it has its MCUs.  With 8 bits or more left such a block is damage: ST_WRITE, and ST_BLOCK_TOTAL
+// once it is complete - what the scan's total said of it before padding could add to the count.
 template <bool WRITE>
 JPEG_DEC_HD inline uint32_t step(const Stream& s, uint32_t& p, uint32_t& bz, uint32_t end, uint32_t seg_end, int16_t* coef,
                                  uint32_t blk0, uint32_t nblk, uint32_t& status) {
@@ -415,6 +419,10 @@ JPEG_DEC_HD inline uint32_t step(const Stream& s, uint32_t& p, uint32_t& bz, uin
         const uint32_t top = peek32(s, p);
         const uint32_t left = seg_end - p;                // > 0: p < end <= seg_end
         if (left < 8 && (top >> (32 - left)) == (1u << left) - 1) {
+            p = seg_end;
+            break;
+        }
+        if (WRITE && z == 0 && left < 8 && blk0 + done == nblk) {   // padding that is not 1-bits, behind the last block
             p = seg_end;
             break;
         }
@@ -446,6 +454,7 @@ JPEG_DEC_HD inline uint32_t step(const Stream& s, uint32_t& p, uint32_t& bz, uin
             ++z;
         }
         if (last || z >= 64) {
+            if (WRITE && blk0 + done >= nblk) status |= ST_BLOCK_TOTAL;   // a whole block more than the segment has
             ++done;
             z = 0;
             b = b + 1 < s.bpm ? b + 1 : 0;
@@ -767,7 +776,7 @@ __device__ inline void jpeg_dec_huff_segment(const jpeg_dec::Stream& s, const Jp
         if (i < n) f.first[sub0 + i] = carry + ex;
         carry += total;
     }
-    if (carry != nblk) status |= ST_BLOCK_TOTAL;
+    if (carry < nblk) status |= ST_BLOCK_TOTAL;          // above: padding decoded as blocks, or damage - the writing pass tells which
     // the writing pass, from the true states
     for (unsigned int i = tid; i < n; i += T) {
         unsigned int p = i ? A[i - 1].x : p0, bz = i ? A[i - 1].y : 0;
