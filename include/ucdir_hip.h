@@ -339,7 +339,12 @@ int32_t ucdir_diffjpeg(const float* x, float* y, const float* factors, int32_t B
  * Copy the activation a layer produced in the last forward into dst as (B,C,Hc,Wc) fp32 NCHW
  * (Hc, Wc = compute size).  layer = state_dict prefix ("downs.0", "ups.7", "mid.0", ...),
  * what = "out" (layer output), "h1" (swish(conv1) inside a block), or "attw" (a block's eight time weights,
- * noise_func(noise_level_mlp(PosEnc(level))), (B,8) fp32: model/ucdir.py:24-29,106,125,212-214). */
+ * noise_func(noise_level_mlp(PosEnc(level))), (B,8) fp32: model/ucdir.py:24-29,106,125,212-214).  Also "res" (the block's
+ * res_conv output) and "bo" (the block output before attention) where the block has them.  "padded:out" | "padded:h1" |
+ * "padded:res" | "padded:bo" copy the whole zero-bordered tensor, (B,C,H+2,W+2) fp32 with the tensor at [1:-1, 1:-1]: the
+ * border cells are zeroed when a shape is planned and no kernel may write them (the activation plan).
+ * Refused while the planned shape recycles its activation buffers (above 512 x 512 compute positions unless
+ * UCDIR_KEEP_ACTS is set, or as the "reuse_acts" flag below forces). */
 int32_t ucdir_debug_read(ucdir_ctx* ctx, const char* layer, const char* what, float* dst,
                          int64_t dst_elems, void* stream);
 int64_t ucdir_workspace_bytes(const ucdir_ctx* ctx);
@@ -349,9 +354,18 @@ int64_t ucdir_workspace_bytes(const ucdir_ctx* ctx);
  * under-filled grids (UCDIR_SPLITK).  "persist_grid": n > 0 launches the persistent kernels (akgm_ws) with n workgroups
  * instead of one per compute unit, 0 restores the default.  "convsk": 0 = 3x3 convs
  * on conv3x3_halo (the round-3 dispatch), 1 = conv_sk_kernel's persistent 8-wave stream-K kind forced, 2 = its one-shot 4-wave kind
- * forced (both regardless of the size thresholds: tests), -1 = environment default (UCDIR_NO_CONV_SK; the 4-wave kind).  Unknown
- * names are an error. */
+ * forced (both regardless of the size thresholds: tests), -1 = environment default (UCDIR_NO_CONV_SK; the 4-wave kind).
+ * "reuse_acts": 1 = activation buffers are recycled by lifetime at any size, 0 = never, -1 = the default rule (recycled above
+ * 512 x 512 compute positions unless UCDIR_KEEP_ACTS is set); a context remembers the mode it planned with and the next
+ * ucdir_prepare_guide re-plans (dropping captured graphs) when the mode in force differs.  Unknown names are an error. */
 int32_t ucdir_debug_flag(const char* name, int32_t value);
+/* The activation-buffer assignment ucdir_prepare_guide would make for (cfg, B, H, W, pad_mode), callable without a device
+ * (tests): one row of six int32 per planned tensor, in planning order: layer index (execution order), which (0 out, 1 h1,
+ * 2 res, 3 bo), H, W, C, buffer id.  Tensors with the same id share one buffer.  reuse: 0 never, 1 always, -1 the default
+ * rule.  Returns the number of tensors (at most `cap` rows are written), or -1 with ucdir_last_error set on a shape the
+ * planner refuses.  Additive in ABI 5. */
+int32_t ucdir_debug_act_plan(const ucdir_config* cfg, int32_t B, int32_t H, int32_t W, int32_t pad_mode, int32_t reuse,
+                             int32_t cap, int32_t* rows);
 /* Host-side launch planning, callable without a device (tests): what = "ksplit" -> the K-split factor conv3x3_halo would use
  * for a grid of `wgs` workgroups over `nchunks` 32-channel chunks of `steps_per_chunk` K steps producing `out_elems` outputs;
  * what = "usplit" -> the unit split (1 | 2 | 4) of the 64-per-group AKGM kernel for `wgs` workgroups;
@@ -392,7 +406,8 @@ int32_t ucdir_predictor_forward(ucdir_predictor* p, const float* x, float* y, in
 /* Copy an activation of the last predictor forward into dst as (B,C,Hc>>l,Wc>>l) fp32 NCHW (tests), on the padded compute
  * grid Hc = (H/32+1)*32, Wc likewise.  name = the reference module: "conv{l}_1" / "conv{l}_2" (after LeakyReLU, l = 1..9),
  * "pool{l}" (l = 1..4), "upv{l}" (l = 6..9).  C is the CARRIED channel count: 64 for the 32-channel layers, whose upper
- * half is zero.  Unknown names and a wrong dst_elems are errors. */
+ * half is zero.  "padded:<name>" copies the whole zero-bordered tensor, (B,C,(Hc>>l)+2,(Wc>>l)+2), as ucdir_debug_read does.
+ * Unknown names and a wrong dst_elems are errors. */
 int32_t ucdir_predictor_debug_read(ucdir_predictor* p, const char* name, float* dst, int64_t dst_elems, void* stream);
 
 /* ---- LPIPS (AlexNet variant) of the val loop (additive in ABI 5; csrc/lpips.hip.h): for B pairs of uint8 RGB images,

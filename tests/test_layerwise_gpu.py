@@ -131,7 +131,8 @@ def test_layer_by_layer_1024_patch_windows(B):
     4096, conv_sk on many vertical strips, the 128^2 C = 512 AKGM tail past akgm_ws64's LDS limit).  B = 1: one window;
     B = 6: the batch DY3h.forward launches for a full-resolution SID image, windows 0 and 5 emulated.  Above 512^2 the engine
     recycles activation buffers by lifetime and debug_read refuses; UCDIR_KEEP_ACTS=1 keeps every layer (same kernels and
-    launches, separate buffers) but is read once per process, so the forward runs in a fresh child process.  Measured
+    launches, separate buffers) but is read once per process, so the forward runs in a fresh child process.  The recycled
+    plan itself is tested in tests/test_act_reuse_gpu.py (forced at small shapes, bit for bit against the kept one).  Measured
     profiler keys: 1, 22, 23, 24, 101, 105, 111, 113, 114, 115, (116 at B = 6), 120, 121, 127, 128, 129, 130 - each already
     reached by the 256^2 layer-wise test at some batch size (111, the AKGM halo fallback of the 128^2 C = 512 tail, at B = 1):
     what is new is the 1024^2 geometry (strip counts, N = 16384 / 4096, the fallback at another level), not another kernel."""

@@ -344,7 +344,7 @@ def test_sr_val_outputs_match_oracle(tmp_path, monkeypatch):
 # ---- BASELINE configs[2] at its real size ----------------------------------------------------------------------------------------
 def test_full_resolution_patch_batch_equals_single_windows(sid_net):
     """configs[2]: a 1424 x 2128 image (DDPM.test pads it to 1552 x 2256) through DY3h.forward - six 1024^2 windows as ONE
-    engine batch (ActPlanner buffer recycling at B = 6, flash attention at N = 16384) - equals six single-window naiveforward
+    engine batch (act_plan buffer recycling at B = 6, flash attention at N = 16384) - equals six single-window naiveforward
     calls pasted in the reference's order (utils/util.py:119-145); finite; workspace bounded."""
     from ucdir_amd import patch as P
     net, sd = sid_net

@@ -1290,65 +1290,112 @@ static int level_dim(int d, int level) { return d >> level; }
 // border cells), and no re-zeroing pass is needed.  A tensor is released after its last reader in launch order:
 // block internals (h1, res, bo) with their block, a layer input when the layer is done unless it sits on the skip
 // stack, a skip when the up block that pops it is done.
-struct ActPlanner {
-    DevPool& pool; int B; bool reuse;
-    std::map<std::array<int, 3>, std::vector<bf16_t*>> free_;
-    Act get(int h, int w, int C, bool stats = true) {
-        Act a; a.B = B; a.H = h; a.W = w; a.C = C;
-        auto& fl = free_[{h, w, C}];
-        if (reuse && !fl.empty()) { a.p = fl.back(); fl.pop_back(); }
-        else a.p = (bf16_t*)pool.alloc((size_t)a.elems() * sizeof(bf16_t), true);
-        if (stats) a.stats = pool.alloc_stats(B);        // statistics are per logical tensor, never shared
-        return a;
-    }
-    void put(const Act& a) { if (reuse && a.p) free_[{a.H, a.W, a.C}].push_back(a.p); }
-};
+//
+// The assignment is host arithmetic on the layer list alone (act_plan, shown to tests by ucdir_debug_act_plan); plan_shapes
+// allocates one zeroed buffer per id it hands out.  Two invariants carry it (the activation plan): borders are
+// never written, and a later tenant of a buffer is first written strictly after the earlier tenant's last reader, in launch
+// order on one stream.
+enum { ACT_OUT = 0, ACT_H1 = 1, ACT_RES = 2, ACT_BO = 3 };
+struct ActSlot { int layer, which, H, W, C, id; };
 
-static void plan_shapes(ucdir_ctx* c, int B, int H, int W, int pad_mode) {
-    // checked before any state changes, as predictor_plan does: a rejected shape must leave the last plan intact (ucdir_prepare_guide
-    // compares against c->B / H / W / pad_mode, so a half-applied plan would make the next call with the same shape skip re-planning
-    // and launch on an empty plan)
-    const int nlev = c->cfg.n_mults;
-    const int Hc = pad_mode ? (H / 32 + 1) * 32 : H, Wc = pad_mode ? (W / 32 + 1) * 32 : W;
+static int g_reuse_acts = -1;      // ucdir_debug_flag("reuse_acts"): 1 recycle at any size, 0 never, -1 UCDIR_KEEP_ACTS + the 512^2 threshold
+static bool reuse_acts_mode(int mode, int Hc, int Wc) {
+    if (mode >= 0) return mode != 0;
+    return !env().keep_acts && (long long)Hc * Wc > 512LL * 512;
+}
+
+// the compute size of a request; throws on a shape no plan exists for
+static void plan_compute_size(const ucdir_config& cfg, int B, int H, int W, int pad_mode, int& Hc, int& Wc) {
+    const int nlev = cfg.n_mults;
+    Hc = pad_mode ? (H / 32 + 1) * 32 : H; Wc = pad_mode ? (W / 32 + 1) * 32 : W;
     require(B >= 1 && H >= 1 && W >= 1, "B, H, W must be >= 1");
     require(!pad_mode || (H >= 33 && W >= 33), "H, W must be >= 33 (reflect pad)");
     require(Hc % (1 << (nlev - 1)) == 0 && Wc % (1 << (nlev - 1)) == 0, "compute size must be divisible by 2^(levels-1)");
     // no kernel was written for a plane with a side of 1 (halo rows, border classes and the linear tiles all assume H, W >= 2)
     require(Hc >= (2 << (nlev - 1)) && Wc >= (2 << (nlev - 1)), "compute size must be at least 2^levels (the deepest planes need 2 x 2 positions)");
+}
+
+// Every planned tensor of the layer list in planning order (per block: h1, res, out, bo) with the id of the buffer it lives
+// in.  Ids count up from 0 in order of first use; without `reuse` every tensor has its own.
+static std::vector<ActSlot> act_plan(const std::vector<LayerDesc>& layers, int Hc, int Wc, bool reuse) {
+    std::vector<ActSlot> plan;
+    std::map<std::array<int, 3>, std::vector<int>> free_;         // (H, W, C) -> released ids, reused last in first out
+    std::vector<long> out_slot(layers.size(), -1);
+    int nid = 0;
+    auto get = [&](size_t li, int which, int h, int w, int C) {
+        auto& fl = free_[{h, w, C}];
+        int id;
+        if (reuse && !fl.empty()) { id = fl.back(); fl.pop_back(); }
+        else id = nid++;
+        plan.push_back({(int)li, which, h, w, C, id});
+        return (long)plan.size() - 1;
+    };
+    auto put = [&](long s) { if (reuse && s >= 0) free_[{plan[s].H, plan[s].W, plan[s].C}].push_back(plan[s].id); };
+    std::vector<size_t> skips;                   // layer indices whose output sits on the skip stack
+    std::vector<bool> is_skip(layers.size(), false);
+    long cur = -1;
+    for (size_t li = 0; li < layers.size(); ++li) {
+        const LayerDesc& d = layers[li];
+        long x1 = -1;
+        if (d.kind == "stem") out_slot[li] = get(li, ACT_OUT, Hc, Wc, d.cout);
+        else if (d.kind == "down") out_slot[li] = get(li, ACT_OUT, level_dim(Hc, d.level + 1), level_dim(Wc, d.level + 1), d.cout);
+        else if (d.kind == "up") out_slot[li] = get(li, ACT_OUT, level_dim(Hc, d.level - 1), level_dim(Wc, d.level - 1), d.cout);
+        else {
+            const int h = level_dim(Hc, d.level), w = level_dim(Wc, d.level);
+            if (d.skip_c) { require(!skips.empty(), "skip stack underflow"); x1 = (long)skips.back(); skips.pop_back(); }
+            const long h1 = get(li, ACT_H1, h, w, d.cout);
+            const long res = d.cin != d.cout ? get(li, ACT_RES, h, w, d.cout) : -1;
+            out_slot[li] = get(li, ACT_OUT, h, w, d.cout);
+            const long bo = d.attn ? get(li, ACT_BO, h, w, d.cout) : -1;
+            put(h1); put(res); put(bo);                          // dead once the block's last launch has been issued
+        }
+        if (x1 >= 0) put(out_slot[x1]);                           // popped skip: consumed by this block
+        if (cur >= 0 && !is_skip[cur]) put(out_slot[cur]);        // layer input, unless an up block still needs it
+        cur = (long)li;
+        if (d.push_skip) { skips.push_back(li); is_skip[li] = true; }
+    }
+    return plan;
+}
+
+static void plan_shapes(ucdir_ctx* c, int B, int H, int W, int pad_mode) {
+    // checked before any state changes, as predictor_plan does: a rejected shape must leave the last plan intact (ucdir_prepare_guide
+    // compares against c->B / H / W / pad_mode, so a half-applied plan would make the next call with the same shape skip re-planning
+    // and launch on an empty plan)
+    int Hc, Wc;
+    plan_compute_size(c->cfg, B, H, W, pad_mode, Hc, Wc);
+    const bool reuse = reuse_acts_mode(g_reuse_acts, Hc, Wc);
+    const std::vector<ActSlot> slots = act_plan(c->layers, Hc, Wc, reuse);
     c->apool.release();
     if (!c->splitk) HIPC(hipMalloc((void**)&c->splitk, SCRATCH_BYTES));   // (planning never runs under a stream capture)
     c->rt.assign(c->layers.size(), LayerRT());
     c->B = B; c->H = H; c->W = W; c->pad_mode = pad_mode;
     c->Hc = Hc; c->Wc = Wc;
-    c->acts_reused = !env().keep_acts && (long long)c->Hc * c->Wc > 512LL * 512;
-    ActPlanner ap{c->apool, B, c->acts_reused, {}};
+    c->acts_reused = reuse;
+    std::vector<bf16_t*> bufs;                   // by id; an id's buffer is allocated (zeroed) where the plan first uses it
     int maxN = 0, attC = 0;
     double fl = 0;
-    std::vector<size_t> skips;                   // layer indices whose output sits on the skip stack
-    std::vector<bool> is_skip(c->layers.size(), false);
-    long cur = -1;
+    size_t si = 0;
     for (size_t li = 0; li < c->layers.size(); ++li) {
         const LayerDesc& d = c->layers[li];
         LayerRT& r = c->rt[li];
-        long x1 = -1;
+        for (; si < slots.size() && slots[si].layer == (int)li; ++si) {
+            const ActSlot& s = slots[si];
+            Act a; a.B = B; a.H = s.H; a.W = s.W; a.C = s.C;
+            if (s.id == (int)bufs.size()) bufs.push_back((bf16_t*)c->apool.alloc((size_t)a.elems() * sizeof(bf16_t), true));
+            a.p = bufs.at(s.id);
+            if (s.which != ACT_RES) a.stats = c->apool.alloc_stats(B);      // statistics are per logical tensor, never shared
+            (s.which == ACT_OUT ? r.out : s.which == ACT_H1 ? r.h1 : s.which == ACT_RES ? r.res : r.bo) = a;
+        }
         if (d.kind == "stem") {
-            r.out = ap.get(c->Hc, c->Wc, d.cout);
             fl += 2.0 * 9 * d.cin * d.cout * c->Hc * c->Wc;
         } else if (d.kind == "down") {
             const int h = level_dim(c->Hc, d.level + 1), w = level_dim(c->Wc, d.level + 1);
-            r.out = ap.get(h, w, d.cout);
             fl += 2.0 * 9 * d.cin * d.cout * h * w;
         } else if (d.kind == "up") {
             const int h = level_dim(c->Hc, d.level - 1), w = level_dim(c->Wc, d.level - 1);
-            r.out = ap.get(h, w, d.cout);
             fl += 2.0 * 9 * d.cin * d.cout * h * w;
         } else {
             const int h = level_dim(c->Hc, d.level), w = level_dim(c->Wc, d.level);
-            if (d.skip_c) { require(!skips.empty(), "skip stack underflow"); x1 = (long)skips.back(); skips.pop_back(); }
-            r.h1 = ap.get(h, w, d.cout);
-            if (d.cin != d.cout) r.res = ap.get(h, w, d.cout, false);
-            r.out = ap.get(h, w, d.cout);
-            if (d.attn) r.bo = ap.get(h, w, d.cout);
             r.G = (float*)c->apool.alloc((size_t)B * h * w * 8 * sizeof(float));
             const double hw = (double)h * w;
             fl += 2.0 * 9 * d.cin * d.cout * hw + 2.0 * 9 * d.cout * d.cout * hw;
@@ -1359,12 +1406,7 @@ static void plan_shapes(ucdir_ctx* c, int B, int H, int W, int pad_mode) {
                 attC = d.cout;
                 fl += 2.0 * d.cout * 3 * d.cout * hw + 2.0 * d.cout * d.cout * hw + 4.0 * hw * hw * d.cout;
             }
-            ap.put(r.h1); ap.put(r.res); ap.put(r.bo);          // dead once the block's last launch has been issued
         }
-        if (x1 >= 0) ap.put(c->rt[x1].out);                       // popped skip: consumed by this block
-        if (cur >= 0 && !is_skip[cur]) ap.put(c->rt[cur].out);    // layer input, unless an up block still needs it
-        cur = (long)li;
-        if (d.push_skip) { skips.push_back(li); is_skip[li] = true; }
     }
     fl += 2.0 * 9 * c->cfg.inner_channel * c->cfg.channel_mults[0] * c->cfg.out_channel * c->Hc * c->Wc;
     c->flops = fl * B;
@@ -1544,7 +1586,9 @@ int32_t ucdir_prepare_guide(ucdir_ctx* ctx, const float* guide, int32_t B, int32
     require(ctx->finalized, "weights not finalized");
     DevGuard dg(ctx->cfg.device);
     hipStream_t st = (hipStream_t)stream;
-    if (B != ctx->B || H != ctx->H || W != ctx->W || pad_mode != ctx->pad_mode || ctx->rt.empty()) {
+    // (a plan made under another "reuse_acts" mode is as stale as one of another shape)
+    if (B != ctx->B || H != ctx->H || W != ctx->W || pad_mode != ctx->pad_mode || ctx->rt.empty() ||
+        reuse_acts_mode(g_reuse_acts, ctx->Hc, ctx->Wc) != ctx->acts_reused) {
         HIPC(hipStreamSynchronize(st));
         ctx->drop_graphs();
         plan_shapes(ctx, B, H, W, pad_mode);
@@ -1608,9 +1652,13 @@ int32_t ucdir_debug_read(ucdir_ctx* ctx, const char* layer, const char* what, fl
     DevGuard dg(ctx->cfg.device);
     require(!ctx->acts_reused, "ucdir_debug_read: activation buffers of this (large) shape are recycled by lifetime; set "
                                "UCDIR_KEEP_ACTS=1 before planning to keep every layer's tensor");
+    const bool padded = !strncmp(what, "padded:", 7);         // the whole bordered tensor (B, C, H + 2, W + 2), not its interior
+    if (padded) what += 7;
     for (size_t li = 0; li < ctx->layers.size(); ++li) {
         if (ctx->layers[li].name != layer) continue;
         const LayerRT& r = ctx->rt[li];
+        require(!padded || !strcmp(what, "out") || !strcmp(what, "h1") || !strcmp(what, "res") || !strcmp(what, "bo"),
+                "debug_read: padded: takes out, h1, res or bo");
         if (!strcmp(what, "attw")) {          // the block's time weights noise_func(PosEnc + MLP(level)) [B][8] (time_mlp_kernel, fp32)
             require(ctx->layers[li].kind == "block" && ctx->attw != nullptr, "attw: not a residual block");
             require(dst_elems == (int64_t)ctx->B * 8, "debug_read: attw has B * 8 elements");
@@ -1623,9 +1671,10 @@ int32_t ucdir_debug_read(ucdir_ctx* ctx, const char* layer, const char* what, fl
         else if (!strcmp(what, "res")) a = &r.res;
         else if (!strcmp(what, "bo")) a = &r.bo;
         require(a->p != nullptr, "no such activation");
-        const int64_t n = (int64_t)a->B * a->C * a->H * a->W;
+        const int64_t n = padded ? (int64_t)a->elems() : (int64_t)a->B * a->C * a->H * a->W;
         require(n == dst_elems, "debug_read: dst has " + std::to_string(dst_elems) + " elements, activation has " + std::to_string(n));
-        hipLaunchKernelGGL(act_to_nchw_kernel, dim3(2048), dim3(256), 0, (hipStream_t)stream, a->p, dst, a->B, a->C, a->H, a->W);
+        if (padded) hipLaunchKernelGGL(act_to_nchw_padded_kernel, dim3(2048), dim3(256), 0, (hipStream_t)stream, a->p, dst, a->B, a->C, a->H, a->W);
+        else hipLaunchKernelGGL(act_to_nchw_kernel, dim3(2048), dim3(256), 0, (hipStream_t)stream, a->p, dst, a->B, a->C, a->H, a->W);
         HIPC(hipGetLastError());
         return 0;
     }
@@ -1641,6 +1690,7 @@ int32_t ucdir_debug_flag(const char* name, int32_t value) {
     else if (!strcmp(name, "skmix")) g_skmix = value;         // conv_sk_kernel<1, 4, 9> with wide + short units: 1 forced at any size, 0 off, -1 environment + occupancy rule
     else if (!strcmp(name, "convsk")) g_convsk = value;       // stream-K conv: 1 forced at any size, 0 off, -1 environment + work threshold
     else if (!strcmp(name, "persist_grid")) g_persist_grid = value;   // persistent kernels: workgroups per launch (0 = one per CU)
+    else if (!strcmp(name, "reuse_acts")) g_reuse_acts = value < 0 ? -1 : value != 0;   // activation buffers recycled by lifetime: 1 at any size, 0 never, -1 UCDIR_KEEP_ACTS + the 512^2 threshold; the next ucdir_prepare_guide re-plans
     else throw std::runtime_error(std::string("unknown debug flag ") + name);
     API_END
 }
@@ -1669,6 +1719,27 @@ int32_t ucdir_debug_launch_plan(const char* what, int32_t wgs, int32_t nchunks, 
             return ok ? ns * 1000 + nhp : 0;
         }
     } catch (...) {}
+    return -1;
+}
+
+int32_t ucdir_debug_act_plan(const ucdir_config* cfg, int32_t B, int32_t H, int32_t W, int32_t pad_mode, int32_t reuse, int32_t cap,
+                             int32_t* rows) {
+    // pure host logic (no device needed): the buffer assignment plan_shapes would allocate, one row per planned tensor
+    try {
+        require(cfg && (rows || cap <= 0), "null argument");
+        require(cfg->n_mults >= 1 && cfg->n_mults <= UCDIR_MAX_MULTS, "bad n_mults");
+        int Hc, Wc;
+        plan_compute_size(*cfg, B, H, W, pad_mode, Hc, Wc);
+        const std::vector<ActSlot> plan = act_plan(build_layers(*cfg), Hc, Wc, reuse_acts_mode(reuse < 0 ? -1 : reuse != 0, Hc, Wc));
+        for (size_t i = 0; i < plan.size() && (int64_t)i < cap; ++i) {
+            const ActSlot& s = plan[i];
+            const int32_t r[6] = {s.layer, s.which, s.H, s.W, s.C, s.id};
+            for (int k = 0; k < 6; ++k) rows[i * 6 + k] = r[k];
+        }
+        return (int32_t)plan.size();
+    }
+    catch (const std::exception& e) { fail(e.what()); }
+    catch (...) { fail("unknown error"); }
     return -1;
 }
 
@@ -2087,10 +2158,12 @@ int32_t ucdir_predictor_debug_read(ucdir_predictor* p, const char* name, float* 
     API_BEGIN
     require(p && name && dst, "null argument");
     DevGuard dg(p->device);
-    const Act& a = predictor_act(p, name);
-    const int64_t n = (int64_t)a.B * a.C * a.H * a.W;
+    const bool padded = !strncmp(name, "padded:", 7);        // the whole bordered tensor (B, C, H + 2, W + 2), as in ucdir_debug_read
+    const Act& a = predictor_act(p, padded ? name + 7 : name);
+    const int64_t n = padded ? (int64_t)a.elems() : (int64_t)a.B * a.C * a.H * a.W;
     require(n == dst_elems, "predictor_debug_read: dst has " + std::to_string(dst_elems) + " elements, activation has " + std::to_string(n));
-    hipLaunchKernelGGL(act_to_nchw_kernel, dim3(2048), dim3(256), 0, (hipStream_t)stream, a.p, dst, a.B, a.C, a.H, a.W);
+    if (padded) hipLaunchKernelGGL(act_to_nchw_padded_kernel, dim3(2048), dim3(256), 0, (hipStream_t)stream, a.p, dst, a.B, a.C, a.H, a.W);
+    else hipLaunchKernelGGL(act_to_nchw_kernel, dim3(2048), dim3(256), 0, (hipStream_t)stream, a.p, dst, a.B, a.C, a.H, a.W);
     HIPC(hipGetLastError());
     API_END
 }

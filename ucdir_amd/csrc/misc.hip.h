@@ -50,6 +50,17 @@ __global__ void act_to_nchw_kernel(const bf16_t* __restrict__ src, float* __rest
         dst[i] = bf2f(src[(((long long)b * (H + 2) + y + 1) * (W + 2) + x + 1) * C + c]);
     }
 }
+// the whole bordered tensor, border cells included: dst (B, C, H + 2, W + 2) fp32 (debug taps: "borders are never written")
+__global__ void act_to_nchw_padded_kernel(const bf16_t* __restrict__ src, float* __restrict__ dst, int B, int C, int H, int W) {
+    const int Hp = H + 2, Wp = W + 2;
+    long long n = (long long)B * Hp * Wp * C;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        int x = (int)(i % Wp); long long t = i / Wp;
+        int y = (int)(t % Hp); t /= Hp;
+        int c = (int)(t % C); int b = (int)(t / C);
+        dst[i] = bf2f(src[(((long long)b * Hp + y) * Wp + x) * C + c]);
+    }
+}
 // (B,8,H,W) fp32 NCHW -> compact [B][H*W][8] fp32 (AKGM modulation, tests)
 __global__ void nchw8_to_compact_kernel(const float* __restrict__ src, float* __restrict__ dst, int B, int H, int W) {
     long long n = (long long)B * H * W * 8;

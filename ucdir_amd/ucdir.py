@@ -70,6 +70,41 @@ def _param_signature(ps):
     return (len(ps), sum(p._version for p in ps), ps[0].data_ptr(), ps[-1].data_ptr(), chk)
 
 
+def _engine_config(cfg: UNetConfig, device=0, attn_fp16=False):
+    """``ucdir_config`` of a UNetConfig."""
+    c = _lib.UcdirConfig()
+    c.in_channel, c.out_channel, c.inner_channel = cfg.in_channel, cfg.out_channel, cfg.inner_channel
+    c.n_mults = len(cfg.channel_mults)
+    for i, v in enumerate(cfg.channel_mults):
+        c.channel_mults[i] = v
+    c.n_attn_res = len(cfg.attn_res)
+    for i, v in enumerate(cfg.attn_res):
+        c.attn_res[i] = v
+    c.res_blocks, c.image_size, c.device = cfg.res_blocks, cfg.image_size, device
+    c.attn_fp16 = 1 if attn_fp16 else 0
+    return c
+
+
+ACT_WHICH = ("out", "h1", "res", "bo")
+
+
+def debug_act_plan(cfg: UNetConfig, B, H, W, pad_mode=1, reuse=-1):
+    """The engine's activation-buffer assignment for a shape, without a device (tests): a list of
+    ``(layer index, which, H, W, C, buffer id)`` with ``which`` in ACT_WHICH, one entry per planned tensor in planning
+    order.  ``reuse``: 0 never, 1 always, -1 the default rule (UCDIR_KEEP_ACTS and the 512 x 512 threshold).  A shape the
+    planner refuses raises UcdirError with its message."""
+    L = _lib.load()
+    c = _engine_config(cfg)
+    n = L.ucdir_debug_act_plan(ctypes.byref(c), B, H, W, pad_mode, reuse, 0, None)
+    if n < 0:
+        raise _lib.UcdirError(L.ucdir_last_error().decode())
+    rows = (ctypes.c_int32 * (6 * n))()
+    if L.ucdir_debug_act_plan(ctypes.byref(c), B, H, W, pad_mode, reuse, n, rows) != n:
+        raise _lib.UcdirError("ucdir_debug_act_plan: the tensor count changed between two calls")
+    return [(rows[6 * i], ACT_WHICH[rows[6 * i + 1]], rows[6 * i + 2], rows[6 * i + 3], rows[6 * i + 4], rows[6 * i + 5])
+            for i in range(n)]
+
+
 class DY3h(nn.Module):
     """Conditional UNet denoiser; same signature as the reference's ``DY3h`` (model/ucdir.py:204-207)."""
 
@@ -161,17 +196,7 @@ class DY3h(nn.Module):
             L.ucdir_destroy(self._h)
             self._h, self._wdirty, self._gkey = None, True, None
         if self._h is None:
-            c = _lib.UcdirConfig()
-            cfg = self.cfg
-            c.in_channel, c.out_channel, c.inner_channel = cfg.in_channel, cfg.out_channel, cfg.inner_channel
-            c.n_mults = len(cfg.channel_mults)
-            for i, v in enumerate(cfg.channel_mults):
-                c.channel_mults[i] = v
-            c.n_attn_res = len(cfg.attn_res)
-            for i, v in enumerate(cfg.attn_res):
-                c.attn_res[i] = v
-            c.res_blocks, c.image_size, c.device = cfg.res_blocks, cfg.image_size, self._device_index()
-            c.attn_fp16 = 1 if self.attn_dtype == "fp16" else 0
+            c = _engine_config(self.cfg, self._device_index(), self.attn_dtype == "fp16")
             h = ctypes.c_void_p()
             _lib.check(L.ucdir_create(ctypes.byref(c), ctypes.byref(h)))
             self._h = h
@@ -199,6 +224,12 @@ class DY3h(nn.Module):
         self.use_graph = bool(on)
         if self._h is not None:
             _lib.check(_lib.load().ucdir_set_graph(self._h, 1 if on else 0))
+
+    def set_reuse_acts(self, mode=-1):
+        """Tests: ``ucdir_debug_flag("reuse_acts")`` - 1 recycles activation buffers by lifetime at any size, 0 never, -1 the
+        default rule.  The flag is process-wide; this module's next forward re-plans under it."""
+        _lib.check(_lib.load().ucdir_debug_flag(b"reuse_acts", int(mode)))
+        self._gkey = None
 
     def _dev(self):
         return torch.device("cuda", self._device_index())
@@ -267,10 +298,12 @@ class DY3h(nn.Module):
         return self.forward_split(x[:, :3], x[:, 3:], time, guide, pad_mode=1)
 
     def debug_read(self, layer, what="out"):
-        """Activation of ``layer`` from the last forward as (B,C,Hc,Wc) fp32 (tests)."""
+        """Activation of ``layer`` from the last forward as (B,C,Hc,Wc) fp32 (tests).  ``what``: out | h1 | res | bo | attw, or
+        ``padded:`` + one of the first four for the whole zero-bordered tensor (B,C,Hc+2,Wc+2)."""
         L = _lib.load()
         from .spec import unet_layers
         B, Hc, Wc = self._last_shape
+        brd = 2 if what.startswith("padded:") else 0
         for Ld in unet_layers(self.cfg):
             if Ld.name == layer and what == "attw":       # the block's time weights, (B, 8) fp32
                 out = torch.empty(B, 8, device=next(self.parameters()).device)
@@ -279,7 +312,7 @@ class DY3h(nn.Module):
                 return out
             if Ld.name == layer:
                 lvl = Ld.level + (1 if Ld.kind == "down" else (-1 if Ld.kind == "up" else 0))
-                out = torch.empty(B, Ld.cout, Hc >> lvl, Wc >> lvl, device=next(self.parameters()).device)
+                out = torch.empty(B, Ld.cout, (Hc >> lvl) + brd, (Wc >> lvl) + brd, device=next(self.parameters()).device)
                 _lib.check(L.ucdir_debug_read(self._handle(), layer.encode(), what.encode(), _ptr(out), out.numel(),
                                               _stream_ptr(self._dev())))
                 return out
@@ -512,9 +545,10 @@ class UNetSeeInDark(nn.Module):
     def debug_read(self, name):
         """Activation ``name`` of the last forward (reference module names: conv{l}_1 / conv{l}_2 after LeakyReLU, pool{l},
         upv{l}) as (B, C, Hc >> l, Wc >> l) fp32 on the padded grid (tests).  C is the carried count: 64 for the 32-channel
-        layers, whose upper half is zero."""
+        layers, whose upper half is zero.  ``padded:<name>``: the whole zero-bordered tensor, two rows and columns more."""
         import re
-        m = re.fullmatch(r"conv([1-9])_[12]|pool([1-4])|upv([6-9])", name)
+        brd = 2 if name.startswith("padded:") else 0
+        m = re.fullmatch(r"conv([1-9])_[12]|pool([1-4])|upv([6-9])", name[7:] if brd else name)
         if m is None or getattr(self, "_last_shape", None) is None:
             raise KeyError(name)
         B, H, W = self._last_shape
@@ -527,7 +561,7 @@ class UNetSeeInDark(nn.Module):
             ch = lvl - 1                      # max pooling keeps the channels of the level above
         else:
             lvl = ch = 9 - int(m.group(3))
-        out = torch.empty(B, max(64, 32 << ch), Hc >> lvl, Wc >> lvl, device=next(self.parameters()).device)
+        out = torch.empty(B, max(64, 32 << ch), (Hc >> lvl) + brd, (Wc >> lvl) + brd, device=next(self.parameters()).device)
         _lib.check(_lib.load().ucdir_predictor_debug_read(self._handle(), name.encode(), _ptr(out), out.numel(),
                                                           _stream_ptr(out.device)))
         return out
