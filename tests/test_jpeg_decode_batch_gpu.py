@@ -2,8 +2,9 @@
 for byte Pillow's Image.open(...).convert("RGB") - the whole matrix in one call, more work items than workgroups with a file
 switch on every item, a long stream next to tiny ones (and the device's per-file round counts are the model's), per-file crops
 and bgr - a damaged file is refused alone, the C interface checks its arguments, and the loaders' prefetch and
-``sr.py --decode-batch`` give what the file-by-file path gives.  The single-file jpeg_decode_device is a second witness.  Output
-and workspace are filled with 0xA5 before every call through the C interface."""
+``sr.py --decode-batch`` give what the file-by-file path gives.  The single-file jpeg_decode_device is a second witness.  Every
+call through raw() runs on buffers between guard bands, at the header's minimum alignment, filled with 0xFF and then with 0xA5
+(tests/guarded.py)."""
 import importlib.util
 import os
 
@@ -11,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import guarded as G
 import jpeg_decode_batch_util as U
 import jpeg_decode_model as D
 from ucdir_amd import lib
@@ -21,23 +23,38 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def raw(datas, crops=None, bgr=False, gap=0):
-    """ucdir_jpeg_decode_batch_profile on poisoned buffers -> (pixels per file, status words, rounds per file, stage times)."""
-    from ucdir_amd.ucdir import _ptr, _stream_ptr
+    """ucdir_jpeg_decode_batch_profile, once per poison byte of guarded.FILLS, on buffers between guard bands at exactly the alignment
+    the header promises (uploaded buffer and workspace 16, status words 4, pixels 1), everything filled with the poison: no guard
+    and no byte of the uploaded buffer changes, and the status words, the rounds and the pixels of every file whose status is 0 do
+    not depend on the poison.  -> (pixels per file, status words, rounds per file, stage times) of the 0xA5 run."""
+    from ucdir_amd.ucdir import _stream_ptr
     L = lib.load()
     b = U.Batch(datas, crops, gap=gap)
     assert b.rc > 0, b.error
     buf = torch.from_numpy(b.buf)
-    buf_dev = buf.cuda()
-    ws = torch.full((b.ws_bytes,), 0xA5, dtype=torch.uint8, device="cuda")
-    out = torch.full((sum(b.out_sizes),), 0xA5, dtype=torch.uint8, device="cuda")
-    status = torch.full((b.n,), -1, dtype=torch.int32, device="cuda")
-    ms, rounds = np.zeros(4, np.float32), np.full(b.n, -1, np.int32)
-    lib.check(L.ucdir_jpeg_decode_batch_profile(_ptr(buf_dev), buf.data_ptr(), buf.numel(), _ptr(out), out.numel(), 1 if bgr else 0,
-                                                _ptr(ws), ws.numel(), _ptr(status), _stream_ptr(out.device), ms.ctypes.data,
-                                                rounds.ctypes.data))
-    o = out.cpu().numpy()
-    pix = [o[int(a):int(a) + s].reshape(c[3], c[2], 3) for a, s, c in zip(b.out_off, b.out_sizes, b.crops)]
-    return pix, status.cpu().tolist(), rounds.tolist(), ms
+    runs = []
+    for fill in G.FILLS:
+        buf_dev = G.Arena(buf.numel(), 16, fill, "cuda")
+        buf_dev.upload(buf)
+        ws = G.Arena(b.ws_bytes, 16, fill, "cuda")
+        out = G.Arena(sum(b.out_sizes), 1, fill, "cuda")
+        status = G.Arena(4 * b.n, 4, fill, "cuda")
+        ms, rounds = np.zeros(4, np.float32), np.full(b.n, -1, np.int32)
+        lib.check(L.ucdir_jpeg_decode_batch_profile(G.ptr(buf_dev), buf.data_ptr(), buf.numel(), G.ptr(out), out.nbytes, 1 if bgr else 0,
+                                                    G.ptr(ws), ws.nbytes, G.ptr(status), _stream_ptr(out.buf.device), ms.ctypes.data,
+                                                    rounds.ctypes.data))
+        torch.cuda.synchronize()
+        for name, a in (("buffer_dev", buf_dev), ("workspace", ws), ("out", out), ("status_dev", status)):
+            a.check_guards(f"{name} (fill {fill:#04x})")
+        assert np.array_equal(buf_dev.bytes(), b.buf), fill
+        o = out.bytes()
+        pix = [o[int(a):int(a) + s].reshape(c[3], c[2], 3) for a, s, c in zip(b.out_off, b.out_sizes, b.crops)]
+        runs.append((pix, status.view(torch.int32, (b.n,)).cpu().tolist(), rounds.tolist(), ms))
+    (pix_ff, st_ff, r_ff, _), (pix, st, r, ms) = runs
+    assert st_ff == st and r_ff == r, (st_ff, st, r_ff, r)
+    for k, (p, q) in enumerate(zip(pix_ff, pix)):
+        assert st[k] != 0 or np.array_equal(p, q), (k, int((p != q).sum()))
+    return pix, st, r, ms
 
 
 def both(datas, crops=None, bgr=False):
@@ -122,6 +139,18 @@ def test_per_file_crops_and_bgr():
     with pytest.raises(ValueError, match="crops"):
         Metrics.jpeg_decode_batch_device(datas[:2], [None])
     assert Metrics.jpeg_decode_batch_device([]) == []
+
+
+def test_crops_off_the_mcu_grid_stand_between_their_guards():
+    """Every file cropped from a corner that is no multiple of 16 (nor of 8): ``out`` holds the crops alone, back to back, between
+    the guard bands raw() checks; a pixel written by its place in the image lands in a neighbour's crop or in a guard."""
+    datas = [D.pillow_file("real", 45, 70, 85, 2, restart_marker_rows=1), D.pillow_file("real", 45, 70, 85, 1),
+             D.pillow_file("real", 45, 70, 85, 0, optimize=True), D.pillow_file("real", 45, 70, 85, "L")]
+    crops = [(13, 7, 37, 29), (17, 19, 53, 26), (1, 1, 68, 43), (69, 44, 1, 1)]
+    pix, status, _, _ = raw(datas, crops, gap=1)
+    assert status == [0] * 4
+    for k, (p, d, (x0, y0, w, h)) in enumerate(zip(pix, datas, crops)):
+        assert np.array_equal(p, D.pillow_decode(d)[y0:y0 + h, x0:x0 + w]), k
 
 
 def test_one_file_and_the_same_bytes_twice():

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import guarded as G
 import jpeg_decode_model as D
 from ucdir_amd import metrics as Metrics
 
@@ -20,21 +21,36 @@ MATRIX = D.matrix()
 
 
 def raw(data, crop=None, bgr=False):
-    """ucdir_jpeg_decode_profile on buffers filled with 0xA5 -> (pixels, status word, fixed-point rounds, stage times)."""
+    """ucdir_jpeg_decode_profile, once per poison byte of guarded.FILLS, on buffers between guard bands at exactly the alignment the
+    header promises (packed stream and workspace 16, status word 4, pixels 1), everything filled with the poison: no guard and no
+    byte of the packed stream changes, and status, rounds and - where the status is 0 - the pixels do not depend on the poison.
+    -> (pixels, status word, fixed-point rounds, stage times) of the 0xA5 run."""
     from ucdir_amd import lib
-    from ucdir_amd.ucdir import _ptr, _stream_ptr
+    from ucdir_amd.ucdir import _stream_ptr
     L = lib.load()
     i = Metrics.jpeg_info(data)
     info = np.array([i[k] for k in Metrics.JPEG_INFO_FIELDS], np.int32)
     x0, y0, w, h = crop or (0, 0, i["width"], i["height"])
-    packed = torch.from_numpy(np.frombuffer(D.pack(data), np.uint8).copy()).cuda()
-    ws = torch.full((L.ucdir_jpeg_decode_workspace_bytes(info.ctypes.data),), 0xA5, dtype=torch.uint8, device="cuda")
-    out = torch.full((h, w, 3), 0xA5, dtype=torch.uint8, device="cuda")
-    status = torch.full((1,), -1, dtype=torch.int32, device="cuda")
-    ms, rounds = np.zeros(4, np.float32), np.zeros(1, np.int32)
-    lib.check(L.ucdir_jpeg_decode_profile(_ptr(packed), packed.numel(), info.ctypes.data, _ptr(out), x0, y0, w, h, 1 if bgr else 0,
-                                          _ptr(ws), _ptr(status), _stream_ptr(out.device), ms.ctypes.data, rounds.ctypes.data))
-    return out.cpu().numpy(), int(status.item()), int(rounds[0]), ms
+    stream = torch.from_numpy(np.frombuffer(D.pack(data), np.uint8).copy())
+    runs = []
+    for fill in G.FILLS:
+        packed = G.Arena(stream.numel(), 16, fill, "cuda")
+        packed.upload(stream)
+        ws = G.Arena(L.ucdir_jpeg_decode_workspace_bytes(info.ctypes.data), 16, fill, "cuda")
+        out = G.Arena(h * w * 3, 1, fill, "cuda")
+        status = G.Arena(4, 4, fill, "cuda")
+        ms, rounds = np.zeros(4, np.float32), np.zeros(1, np.int32)
+        lib.check(L.ucdir_jpeg_decode_profile(G.ptr(packed), stream.numel(), info.ctypes.data, G.ptr(out), x0, y0, w, h, 1 if bgr else 0,
+                                              G.ptr(ws), G.ptr(status), _stream_ptr(out.buf.device), ms.ctypes.data, rounds.ctypes.data))
+        torch.cuda.synchronize()
+        for name, a in (("packed_dev", packed), ("workspace", ws), ("out", out), ("status_dev", status)):
+            a.check_guards(f"{name} (fill {fill:#04x})")
+        assert np.array_equal(packed.bytes(), stream.numpy()), fill
+        runs.append((out.bytes().reshape(h, w, 3), int(status.view(torch.int32, (1,)).item()), int(rounds[0]), ms))
+    (pix_ff, st_ff, r_ff, _), (pix, st, r, ms) = runs
+    assert (st_ff, r_ff) == (st, r), ((st_ff, r_ff), (st, r))
+    assert st != 0 or np.array_equal(pix_ff, pix), int((pix_ff != pix).sum())
+    return pix, st, r, ms
 
 
 def gpu(data, crop=None, bgr=False):
@@ -121,6 +137,17 @@ def test_crops_and_bgr():
         for bad in ((0, 0, W + 1, H), (-1, 0, 2, 2), (0, 0, 0, 1), (5, H, 1, 1), "whole"):
             with pytest.raises(ValueError, match="crop"):
                 Metrics.jpeg_decode_device(data, crop=bad)
+
+
+def test_a_crop_off_the_mcu_grid_stands_between_its_guards():
+    """Crops that start at no multiple of 16 (nor of 8): ``out`` holds the crop alone, so everything around it is guard band -
+    a pixel written by its place in the image, not in the crop, lands there (raw() checks the guards)."""
+    for sub, kw in ((2, {"restart_marker_rows": 1}), (1, {}), (0, {"optimize": True}), ("L", {})):
+        data = D.pillow_file("real", 45, 70, 85, sub, **kw)
+        ref = D.pillow_decode(data)
+        for x0, y0, w, h in ((13, 7, 37, 29), (17, 19, 53, 26), (1, 1, 68, 43), (69, 44, 1, 1)):
+            got, status, _, _ = raw(data, crop=(x0, y0, w, h))
+            assert status == 0 and np.array_equal(got, ref[y0:y0 + h, x0:x0 + w]), (sub, x0, y0, w, h)
 
 
 def test_same_bytes_twice():

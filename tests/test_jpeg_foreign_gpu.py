@@ -1,5 +1,5 @@
 """The HIP JPEG decoder (csrc/jpeg_decode.hip.h) on the GPU on files as encoders other than libjpeg write them: every file of
-tests/jpeg_foreign.py's catalogue through ucdir_jpeg_decode_profile on 0xA5-filled buffers and through jpeg_decode_device - the
+tests/jpeg_foreign.py's catalogue through ucdir_jpeg_decode_profile on guarded, poisoned buffers (raw() of tests/test_jpeg_decode_gpu.py) and through jpeg_decode_device - the
 pixels are Pillow's, the model's and the writer's own, byte for byte, the status word is 0 and the rounds are the model's - two
 of them with crops and bgr, the whole catalogue as one batch in both orders, and through the ImagenetSRDataset loader.  The three
 classes that stay refused (jpeg_foreign.MUST_REFUSE) come back with the model's code, never with pixels."""
