@@ -371,7 +371,9 @@ int32_t ucdir_debug_act_plan(const ucdir_config* cfg, int32_t B, int32_t H, int3
  * what = "usplit" -> the unit split (1 | 2 | 4) of the 64-per-group AKGM kernel for `wgs` workgroups;
  * what = "tile" -> th * 1000 + tw of the pixel tile conv3x3_halo / the one-shot AKGM kernels take on a plane of
  * (`wgs`, `nchunks`) = (H, W); what = "sk_strips" -> strips * 1000 + halo pieces per chunk of conv_sk_kernel<MW, NW> on a plane of
- * `wgs` columns, `nchunks` = 10 MW + NW (14 | 28 | 18), 0 if no split fits; what = "last_ksplit" -> the K-split factor the
+ * `wgs` columns, `nchunks` = 10 MW + NW (14 | 28 | 18), 0 if no split fits; what = "sk_halo_cycles" -> the LDS cycles of one
+ * B fragment read of conv_sk_kernel (ds_read_b128 bank rule, brute force; 4 = conflict-free) at a position-space row pitch of
+ * `wgs`, tap `nchunks` (0 .. 8 = 3 ky + kx) and wave column `steps_per_chunk` (0 .. 7); what = "last_ksplit" -> the K-split factor the
  * latest conv3x3_halo launch of this process ran with (1 = unsplit, 0 = none yet; the other arguments are ignored: split and
  * unsplit launches share a profiler key).  -1 on a bad name. */
 int32_t ucdir_debug_launch_plan(const char* what, int32_t wgs, int32_t nchunks, int32_t steps_per_chunk, double out_elems);

@@ -4,26 +4,29 @@
 // its structure: one LDS fragment read per MFMA, 16 MFMAs between two barriers, a prologue / epilogue bubble per workgroup and whole
 // rounds of workgroups (round-3 verdict: 0.32 of the MFMA peak for 38 % of the forward).  This kernel is the structural step:
 //   * ONE workgroup (8 wave64) per CU walks work units; a unit = MW x 128 output rows x NPX = 512 / MW pixel positions
-//     (MW = 2: 256 x 256, C_out multiples of 256; MW = 1: 128 x 512, C_out = 128); a wave owns 128 rows x 64 pixels = 4 x 2 MFMA
-//     tiles of 32 x 32 x 16 - 128 accumulator registers, SIX fragment reads per EIGHT MFMAs (0.75 instead of 1.0);
+//     (MW = 2: 256 x 256, C_out multiples of 256; MW = 1: 128 x 512, C_out = 128); a wave owns 128 rows x 64 pixels = 8 x 4 MFMA
+//     tiles of 16 x 16 x 32 (v_mfma_f32_16x16x32_bf16: the same cycles per FLOP as 32 x 32 x 16, but the chip holds a higher clock under it -
+//     the launches of the bench configuration got 3 - 6 % shorter, profiles/EXPERIMENTS.md) - 128 accumulator registers, TWELVE fragment
+//     reads of 1 KB per 32 MFMAs (the same 12 KB per 512 matrix-pipe cycles as six per eight MFMAs of 32 x 32 x 16);
 //   * pixel tiles are LINEAR in the zero-bordered [B][H + 2][W + 2] position space, batch-flattened: a tile is NPX consecutive
 //     positions (crossing rows and samples), its halo the NPX + 2 Wp + 2 positions around them - one contiguous range of the
-//     tensor.  Tap (ky, kx) of slot s is halo position s + ky Wp + kx: a uniform shift, 16 consecutive lanes always read 16
-//     consecutive halo positions (conflict-free ds_read_b128 at any width), border positions are computed and not stored
+//     tensor.  Tap (ky, kx) of slot s is halo position s + ky Wp + kx: a uniform shift, the 16 positions of a B fragment are always 16
+//     consecutive halo positions (conflict-free ds_read_b128 at any width: sk_halo_chunk), border positions are computed and not stored
 //     (utilisation H W / ((H + 2)(W + 2)): 95 % at 72^2, 90 % at 36^2, 81 % at 18^2 - the 2-D tiles of conv3x3_halo reach 84 / 84 /
 //     63 %); per-sample GroupNorm statistics enter in the EPILOGUE (rstd, mean * rstd per lane), so a tile may span samples;
-//   * K advances one tap x 32 channels per sub-step (16 MFMAs per wave, two k16 units); the weights are packed on the host as the
-//     LDS image of every sub-step (16 KB, fragment-major: a fragment read is 1 KB lane-linear, conflict-free, and every LDS-DMA
-//     piece is 1 KB of contiguous memory) and stream through a FOUR-deep ring: the stage of sub-step h + 4 is requested at sub-step
-//     h and waited for (counted vmcnt) at h + 2, one sub-step before its first read - fragment reads run two units ahead ACROSS the
-//     one barrier per sub-step, which only protects the ring slot being refilled;
+//   * K advances one tap x 32 channels per sub-step (one k32 step: 32 MFMAs per wave in two halves of 16); the weights are packed on the
+//     host as the LDS image of every sub-step (16 KB, fragment-major: a fragment - 16 rows x 32 k - is 1 KB lane-linear, conflict-free, and
+//     every LDS-DMA piece is 1 KB of contiguous memory; pack_conv_sk16) and stream through a FOUR-deep ring: the stage of sub-step h + 4 is
+//     requested at sub-step h and waited for (counted vmcnt) at h + 2, one sub-step before its first read - fragment reads run one sub-step
+//     ahead ACROSS the one barrier per sub-step, which only protects the ring slot being refilled;
 //   * the halo of the next 32-channel chunk arrives under the current chunk (double buffer, 64-byte pixels, 16-byte chunk
-//     XOR (position >> 2) & 3 on the DMA's source side);
+//     XOR 2 ((position >> 2) & 1) on the DMA's source side);
 //   * stream-K: the units that do not fill a whole round of workgroups are cut into chunk ranges dealt evenly to ALL workgroups;
 //     a partial unit leaves raw fp32 accumulators (accumulator layout, coalesced 16-byte stores) in a scratch slot and
 //     conv_sk_finish_kernel sums the parts in ascending workgroup order (fixed: bit-reproducible) and runs the same epilogue;
-//   * epilogue in registers: rows are permuted at pack time so that a lane holds 16 consecutive channels of one pixel per MFMA tile
-//     (32-byte pieces); GroupNorm fold from two sample-independent tables in LDS (bias + Tb, Tg; 9 border classes) and the
+//   * behind the K loop every 32 x 32 block of the wave tile goes through 4 KB of wave-private LDS (the dead weight ring) from its four
+//     16 x 16 tiles into the accumulator layout of the 32 x 32 MFMA with a lane holding 16 consecutive channels of one pixel (32-byte
+//     pieces): the epilogue, the partial tiles and the finish kernel work on that layout; GroupNorm fold from two sample-independent tables in LDS (bias + Tb, Tg; 9 border classes) and the
 //     per-sample (rstd, mean * rstd) list built once per workgroup; output statistics as 2^-20 fixed-point integers.
 // What ships as the default (measured): the SAME wave tile and loop in 4-wave workgroups of 128 rows x 256 positions with
 // 80 KB of LDS, two per CU, one unit each (template <1, 4, NTAPS>): one's prologue / epilogue runs under the other's K loop, the fold tables
@@ -102,6 +105,43 @@ struct CvSk {
 #else
 #define SK_STAMP() do {} while (0)
 #endif
+
+// Where the halo keeps logical 16-byte chunk c (channels 8 c .. + 7 of the 32-channel chunk) of halo position hp inside its 64-byte pixel.
+// A B fragment read takes 16 consecutive positions (lane & 15) x the whole pixel (chunk lane >> 4); a ds_read_b128 lane group ({0-3, 12-15,
+// 20-27}, ...) then holds, for every hp & 3, the four positions hp, hp + 4, hp + 8, hp + 12 with the logical chunks (c, c ^ 1, c ^ 1, c), all in
+// one quarter of the 64 banks: XOR with 0, 2, 0, 2 - bit 2 of the position - puts them into its four different 16-byte slots at any tap shift
+// and row pitch.  (The 32 x 32 loop's XOR with (hp >> 2) & 3 collides here: c ^ s and (c ^ 1) ^ (s + 1) are equal for even s.)
+__host__ __device__ constexpr unsigned sk_halo_chunk(unsigned c, unsigned hp) { return (c ^ ((hp >> 1) & 2u)) & 3u; }
+// LDS cycles of one B fragment read (brute force over the bank rule of ds_read_b128: four lane groups, one cycle each plus one per further
+// distinct address on a busy bank; 64 banks of 4 bytes): wave column wn, tap (ky, kx), row pitch Wpe of the position space.  4 = conflict-free.
+inline int sk_halo_read_cycles(int Wpe, int ky, int kx, int wn) {
+    static const int group_of[16] = {0, 0, 0, 0, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0};   // lanes 0 - 15; lanes 16 - 31: the other group; 32 - 63: + 2
+    int cycles = 0;
+    for (int grp = 0; grp < 4; ++grp) {
+        unsigned addr_of_bank[64][16]; int n_of_bank[64] = {0};
+        for (int lane = 0; lane < 64; ++lane) {
+            const int g = (lane >> 5) * 2 + ((lane & 16) ? 1 - group_of[lane & 15] : group_of[lane & 15]);
+            if (g != grp) continue;
+            const unsigned hp = (unsigned)(wn * 64 + (lane & 15) + ky * Wpe + kx);
+            const unsigned addr = (hp << 6) + (sk_halo_chunk((unsigned)(lane >> 4), hp) << 4);
+            for (int d = 0; d < 4; ++d) {
+                const int bank = (int)((addr / 4 + d) & 63);
+                bool seen = false;
+                for (int i = 0; i < n_of_bank[bank]; ++i) seen = seen || addr_of_bank[bank][i] == addr;
+                if (!seen) addr_of_bank[bank][n_of_bank[bank]++] = addr;
+            }
+        }
+        int worst = 1;
+        for (int b = 0; b < 64; ++b) worst = n_of_bank[b] > worst ? n_of_bank[b] : worst;
+        cycles += worst;
+    }
+    return cycles;
+}
+
+// A lane index the compiler cannot see through: addresses formed from it are formed where they are used.  Formed from `lane` itself they are
+// invariants of the segment loop, hoisted in front of it and alive across the K loop, which has no register to spare (the 16 x 16 x 32 loop
+// spilled eight of them).
+__device__ __forceinline__ int sk_opaque(int v) { asm volatile("" : "+v"(v)); return v; }
 
 template <int N>
 __device__ __forceinline__ void sk_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
@@ -447,8 +487,10 @@ __device__ __forceinline__ void conv_sk_body(const ConvSkP& p, unsigned char* sm
                                              const int qbase, const int nhp) {
     using L = CvSk<MW, NW>;
     static_assert(NF == 4 || (NF == 2 && MW == 1 && NW == 4), "short units: four waves of 64 x 64");
+    static_assert(NW * 4096 <= 4 * L::STAGE, "the layout conversion's 4 KB per wave come out of the weight ring");
     constexpr int PWN = L::PW * NF / 4;                              // DMA pieces per wave and stage
     constexpr int RSUB = 4 / NF;                                     // units per 128-row tile
+    constexpr int NA = 2 * NF, HA = NF;                              // A fragments (16 rows) of a wave tile; of one half of a sub-step
     constexpr int NWN = L::NWN;                                      // waves along the pixel dimension
     const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hh = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -469,29 +511,30 @@ __device__ __forceinline__ void conv_sk_body(const ConvSkP& p, unsigned char* sm
     constexpr int HPER = (NHW + TA - 1) / TA;                        // pieces per such S point
 
     // ---- per-lane constants of the fragment reads ------------------------------------------------------------------------
-    // A: stage slot s, fragment f (32 rows), k16 j: 1 KB lane-linear at s * STAGE + ((4 wm + f) * 2 + j) * 1024 + lane * 16
-    // (short units: their 4 KB - fragments 0, 1 of the slot - sit at the slot's start)
+    // A: stage slot s, fragment R (16 rows x 32 k): 1 KB lane-linear at s * STAGE + (8 wm + R) * 1024 + lane * 16
+    // (short units: their 4 KB - fragments 0 .. 3 of the slot - sit at the slot's start)
     const unsigned a_lane = L::OFF_W + (NF == 4 ? (4 * wm) * 2048 : 0) + lane * 16;
-    // B: tap t, MFMA tile n: halo position hp = 64 wn + 32 n + l31 + ky Wp + kx; 64 bytes per position, 16-byte chunk
-    // (2 jj + hh) ^ ((hp >> 2) & 3): address(jj = 1) = address(jj = 0) ^ 32.  (Upsample parity classes: per segment.)
-    // (the second MFMA tile of a wave is 32 positions = 2048 bytes further with the same swizzle: an immediate offset, not a register)
+    // B: tap t, MFMA tile n (16 positions): halo position hp = 64 wn + 16 n + (lane & 15) + ky Wp + kx; 64 bytes per position, the lane's k group
+    // lane >> 4 is the pixel's 16-byte chunk, stored at chunk sk_halo_chunk(lane >> 4, hp) - 4 LDS cycles per read at any tap shift and row pitch
+    // (sk_halo_read_cycles above is the brute-force check).  (Upsample parity classes: per segment.)  (the further MFMA tiles of a wave are 16 positions = 1024 bytes apart with the same swizzle: immediate
+    // offsets, not registers)
     unsigned bx[NTAPS];
     auto set_bx = [&](int py, int pxp) {
 #pragma unroll
         for (int t = 0; t < NTAPS; ++t) {
             int ky, kx;
             if (NTAPS == 9) { ky = t / 3; kx = t - 3 * ky; } else { ky = py + (t >> 1); kx = pxp + (t & 1); }
-            const int hp = wn * 64 + l31 + ky * Wp + kx;
-            bx[t] = L::OFF_H + (hp << 6) + (((hh ^ (hp >> 2)) & 3) << 4);
+            const int hp = wn * 64 + (lane & 15) + ky * Wp + kx;
+            bx[t] = L::OFF_H + (hp << 6) + (sk_halo_chunk((unsigned)(lane >> 4), (unsigned)hp) << 4);
         }
     };
     if (NTAPS == 9) set_bx(0, 0);
-    // halo staging: piece i = 16 positions; lane -> (position 16 i + lane / 4, physical 16-byte chunk lane & 3 = logical ^ ((pos >> 2) & 3));
+    // halo staging: piece i = 16 positions; lane -> (position 16 i + lane / 4, physical 16-byte chunk lane & 3 = logical ^ (2 ((pos >> 2) & 1)));
     // this wave's j-th piece is piece j * NW + wave (past the halo's end: a repeat of its last piece)
-    // (per lane: one base position and one source swizzle - the chunk XOR ((16 i + lane / 4) >> 2) & 3 = (lane >> 4) & 3 does not depend on the
-    // piece; the piece index i of (j, wave) is wave-uniform)
+    // (per lane: one base position and one source swizzle - the chunk XOR 2 (((16 i + lane / 4) >> 2) & 1) = 2 ((lane >> 4) & 1) does not depend on
+    // the piece; the piece index i of (j, wave) is wave-uniform)
     const int hpos0 = (lane >> 2) - Wp - 1;                         // + 16 i + q0: position in the strip space
-    const unsigned hsw = (unsigned)(((lane & 3) ^ ((lane >> 4) & 3)) << 3);
+    const unsigned hsw = sk_halo_chunk((unsigned)(lane & 3), (unsigned)(lane >> 2)) << 3;
     auto piece_of = [&](int j) { const int i = j * NW + wave; return i < nhp ? i : nhp - 1; };
 
     const SkSched sch(units_arg, ndp_arg, nch, G);
@@ -552,12 +595,12 @@ __device__ __forceinline__ void conv_sk_body(const ConvSkP& p, unsigned char* sm
     // halo pieces that the last chunk would request for a chunk that does not exist - same instruction count, idle halo buffer
     constexpr int NTP = 10;
     auto issue_table = [&](int rt, int i, int buf) {                 // piece i = segments 2 i (lanes 0 - 31) and 2 i + 1 (lanes 32 - 63)
-        const int seg = 2 * i + (lane >> 5);
+        const int ln = sk_opaque(lane), seg = 2 * i + (ln >> 5);
         const float* src = reinterpret_cast<const float*>(p.A);      // (a missing array: anything readable; the epilogue does not look at it)
         if (seg == 0 || seg > 18) { if (p.bias) src = p.bias + rt * L::ROWS; }
         else if (seg < 10) { if (p.fold) src = p.Tb + (long long)(seg - 1) * p.tab_ld + rt * L::ROWS; }
         else if (p.fold) src = p.Tg + (long long)(seg - 10) * p.tab_ld + rt * L::ROWS;
-        __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)(src + (lane & 31) * 4), (LDS_AS void*)(smem + L::OFF_H + buf * HB + i * 1024), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)(src + (ln & 31) * 4), (LDS_AS void*)(smem + L::OFF_H + buf * HB + i * 1024), 16, 0, 0);
     };
     int hb0 = 0;                                                     // halo buffer of the segment's first chunk
     auto prefetch = [&](const Seg& s) {                              // halo of the first chunk and stages 0 .. 3 of segment s
@@ -597,7 +640,7 @@ __device__ __forceinline__ void conv_sk_body(const ConvSkP& p, unsigned char* sm
         const int per_b = p.ns * p.HpWpe;
         const int b0 = sk_udiv(qbase + s.tile * L::NPX, per_b, p.inv_per_b);
         int b1 = sk_udiv(qbase + s.tile * L::NPX + L::NPX - 1, per_b, p.inv_per_b) + 1; b1 = b1 < p.nb ? b1 : p.nb;
-        if (b0 < b1) sk_sample_table(p, reinterpret_cast<float*>(smem + L::OFF_MS) + 2 * b0, b0, b1, wave, NW, lane);
+        if (b0 < b1) sk_sample_table(p, reinterpret_cast<float*>(smem + L::OFF_MS) + 2 * b0, b0, b1, wave, NW, sk_opaque(lane));
     };
     if (L::LDS_TAB) {
         sk_sample_table(p, reinterpret_cast<float*>(smem + L::OFF_MS), 0, p.nb, wave, NW, lane);
@@ -608,38 +651,39 @@ __device__ __forceinline__ void conv_sk_body(const ConvSkP& p, unsigned char* sm
     while (true) {
         const Seg nxt = next_segment();
         const int cb = cur.cb, ce = cur.ce;
-        f32x16_t acc[NF][2];
+        // the wave tile as NA x 4 tiles of 16 x 16 (v_mfma_f32_16x16x32_bf16): tile (R, n), register i of lane l = row 16 R + 4 (l >> 4) + i,
+        // position 16 n + (l & 15)
+        f32x4_t c16[NA][4];
 #pragma unroll
-        for (int f = 0; f < NF; ++f)
+        for (int r = 0; r < NA; ++r)
 #pragma unroll
-            for (int n = 0; n < 2; ++n)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[f][n][e] = 0.f;
+            for (int n = 0; n < 4; ++n) c16[r][n] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
-        HC_WAIT(0);                                                  // this segment's first halo and stages 0 .. 3 (requested under the previous epilogue)
+        HC_WAIT(0);                                                 // this segment's first halo and stages 0 .. 3 (requested under the previous epilogue)
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         SK_STAMP();
 
-        bf16x8_t fa[2][NF], fb[2][2];
-        // R(t, jj) of sub-step h: A from slot h & 3, B from the halo buffer of its chunk
-        auto reads = [&](auto tc, auto jc, int h, unsigned boff) {
-            constexpr int t = decltype(tc)::value, jj = decltype(jc)::value;
-            const unsigned aa = a_lane + (unsigned)((h & 3) * L::STAGE);
-            lds_read16_asm<0 * 2048 + jj * 1024>(fa[jj][0], aa);
-            lds_read16_asm<1 * 2048 + jj * 1024>(fa[jj][1], aa);
-            if constexpr (NF == 4) {
-                lds_read16_asm<2 * 2048 + jj * 1024>(fa[jj][2], aa);
-                lds_read16_asm<3 * 2048 + jj * 1024>(fa[jj][3], aa);
-            }
-            const unsigned b0 = (bx[t] + boff) ^ (jj << 5);
-            lds_read16_asm<0>(fb[jj][0], b0);
-            lds_read16_asm<2048>(fb[jj][1], b0);
-        };
+        // the NA + 4 fragments of one sub-step (one tap x 32 channels): A fragment R from the stage's slot, B fragment n from the halo buffer of its
+        // chunk.  They are requested - and, LDS reads returning in order, they land - in the order the MFMAs below free their registers:
+        // fa[0 .. HA), fb[0], fb[1], fb[2], fa[HA .. NA), fb[3]
+        bf16x8_t fa[NA], fb[4];
+#ifdef SK_ABL_NOREAD
+        auto rd_a = [&](auto, unsigned) {};
+        auto rd_b = [&](auto, unsigned) {};
+#else
+        auto rd_a = [&](auto rc, unsigned aa) { constexpr int r = decltype(rc)::value; lds_read16_asm<r * 1024>(fa[r], aa); };
+        auto rd_b = [&](auto nc, unsigned b0) { constexpr int n = decltype(nc)::value; lds_read16_asm<n * 1024>(fb[n], b0); };
+#endif
         __builtin_amdgcn_sched_barrier(0);
         unsigned bcur = hb0 ? (unsigned)HB : 0u;                     // halo buffer offset of the current chunk (0 | HB)
-        reads(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, 0, bcur);
-        reads(std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{}, 0, bcur);
+        {
+            const unsigned b0 = bx[0] + bcur;                        // sub-step 0: slot 0
+            static_for<0, HA>([&](auto rc) { rd_a(rc, a_lane); });
+            static_for<0, 3>([&](auto nc) { rd_b(nc, b0); });
+            static_for<HA, NA>([&](auto rc) { rd_a(rc, a_lane); });
+            rd_b(std::integral_constant<int, 3>{}, b0);
+        }
 
         int h = 0;                                                   // sub-step counter of this segment
         const bool want_tab = !L::LDS_TAB && cb == 0 && ce == nch;   // (a partial segment has no epilogue)
@@ -652,47 +696,38 @@ __device__ __forceinline__ void conv_sk_body(const ConvSkP& p, unsigned char* sm
                 constexpr int t = decltype(tc)::value;
                 constexpr int tn = (t + 1) % NTAPS;
                 constexpr int tm1 = (t + NTAPS - 1) % NTAPS;
-                // A unit's eight MFMAs in program order with the NEXT-BUT-ONE unit's fragment reads (and, in a sub-step's second unit, the S
-                // point's DMA pieces) placed in their shadows: a wave issues in order, so an instruction behind the cluster would wait for
-                // all eight (a lone wave per SIMD ran the cluster-then-reads order at 54 % of the matrix pipe).  A fragment register is
-                // re-requested right behind the last MFMA that reads it; sched_barrier pins the order.
+                // The sub-step's 8 HA MFMAs in program order with the NEXT sub-step's fragment reads (and, in the second half, the S point's DMA
+                // pieces) placed in their shadows: a wave issues in order, so an instruction behind the cluster would wait for all of it (a lone
+                // wave per SIMD ran the cluster-then-reads order at 54 % of the matrix pipe).  A fragment register is re-requested right behind
+                // the last MFMA that reads it - at least 3 HA MFMAs before its next use; sched_barrier pins the order.
                 const unsigned boffn = tn == 0 ? bnext : bcur;
                 const unsigned aan = a_lane + (unsigned)(((h + 1) & 3) * L::STAGE);        // sub-step h + 1: slot, halo buffer
-                auto unit = [&](auto jc, auto&& shadow) {
-                    constexpr int jj = decltype(jc)::value;
-                    const unsigned b0 = (bx[tn] + boffn) ^ (jj << 5);
-#define SK_MF(f, n) acc[f][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[jj][f], fb[jj][n], acc[f][n], 0, 0, 0); __builtin_amdgcn_sched_barrier(0)
-                    if constexpr (NF == 2) {
-                        // four MFMAs; every fragment register re-requested right behind the last MFMA that reads it
-                        SK_MF(0, 0); shadow(std::integral_constant<int, 0>{}); __builtin_amdgcn_sched_barrier(0);
-                        SK_MF(1, 0); lds_read16_asm<0>(fb[jj][0], b0); shadow(std::integral_constant<int, 1>{}); __builtin_amdgcn_sched_barrier(0);
-                        SK_MF(0, 1); lds_read16_asm<0 * 2048 + jj * 1024>(fa[jj][0], aan); shadow(std::integral_constant<int, 2>{}); __builtin_amdgcn_sched_barrier(0);
-                        SK_MF(1, 1); lds_read16_asm<1 * 2048 + jj * 1024>(fa[jj][1], aan); lds_read16_asm<2048>(fb[jj][1], b0); __builtin_amdgcn_sched_barrier(0);
-                    } else {
-                    SK_MF(0, 0); shadow(std::integral_constant<int, 0>{}); __builtin_amdgcn_sched_barrier(0);
-                    SK_MF(1, 0); shadow(std::integral_constant<int, 1>{}); __builtin_amdgcn_sched_barrier(0);
-                    SK_MF(2, 0); shadow(std::integral_constant<int, 2>{}); __builtin_amdgcn_sched_barrier(0);
-#ifdef SK_ABL_NOREAD
-                    SK_MF(3, 0); SK_MF(0, 1); SK_MF(1, 1); SK_MF(2, 1); SK_MF(3, 1); (void)b0; (void)aan;
-#else
-                    SK_MF(3, 0); lds_read16_asm<0>(fb[jj][0], b0); __builtin_amdgcn_sched_barrier(0);
-                    SK_MF(0, 1); lds_read16_asm<0 * 2048 + jj * 1024>(fa[jj][0], aan); __builtin_amdgcn_sched_barrier(0);
-                    SK_MF(1, 1); lds_read16_asm<1 * 2048 + jj * 1024>(fa[jj][1], aan); __builtin_amdgcn_sched_barrier(0);
-                    SK_MF(2, 1); lds_read16_asm<2 * 2048 + jj * 1024>(fa[jj][2], aan); __builtin_amdgcn_sched_barrier(0);
-                    SK_MF(3, 1); lds_read16_asm<3 * 2048 + jj * 1024>(fa[jj][3], aan); lds_read16_asm<2048>(fb[jj][1], b0); __builtin_amdgcn_sched_barrier(0);
+                const unsigned b0n = bx[tn] + boffn;
+                // one k32 step = two halves of 4 x HA MFMAs: half hf takes the A fragments hf HA .. + HA - 1 against all four B fragments, B outermost
+                auto half = [&](auto hc, auto&& shadow) {
+                    constexpr int hf = decltype(hc)::value;
+                    static_for<0, 4 * HA>([&](auto mc) {
+                        constexpr int m = decltype(mc)::value, n = m / HA, r = hf * HA + m % HA;
+                        if constexpr (hf == 0 && m % HA == 0) {
+                            // fa[0 .. HA) and fb[0 .. n] landed; before the last group that is every read of stage h (fb[3] was requested last)
+#ifndef SK_ABL_NOREAD
+                            lgkm_wait_asm<n == 3 ? 0 : HA + 3 - n>();
 #endif
-                    }
-#undef SK_MF
+                        }
+                        // (as a statement with the accumulator tied: left to the builtin, hipcc gives a 4-register result a register of its own and
+                        // rotates accumulators and fragments through 196 registers - 58 spilled, scratch loads inside this loop.  Nothing in the loop
+                        // consumes an MFMA result but the same accumulator's next MFMA, 4 HA instructions later; the drain below covers the first use)
+                        asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(c16[r][n]) : "v"(fa[r]), "v"(fb[n]));
+                        __builtin_amdgcn_sched_barrier(0);
+                        if constexpr (hf == 1 && m < 3) shadow(mc);
+                        if constexpr (n == 3) rd_a(std::integral_constant<int, r>{}, aan);            // the last MFMA that reads fa[r]
+                        if constexpr (hf == 1 && m % HA == HA - 1) rd_b(std::integral_constant<int, n>{}, b0n);   // ... that reads fb[n]
+                        __builtin_amdgcn_sched_barrier(0);
+                    });
                 };
-                // ---- unit (t, 0) ----
-#ifndef SK_ABL_NOREAD
-                lgkm_wait_asm<NF + 2>();                             // R(t, 0) landed (R(t, 1) may be in flight)
-#endif
-                unit(std::integral_constant<int, 0>{}, [&](auto) {});
-                // ---- unit (t, 1) ----
-#ifndef SK_ABL_NOREAD
-                lgkm_wait_asm<NF + 2>();                             // R(t, 1) landed: every read of stage h is complete
-#endif
+                // ---- first half ----
+                half(std::integral_constant<int, 0>{}, [&](auto) {});
+                // ---- second half ----
                 {
                     // S point: stage h + 2 must be in LDS (requested two sub-steps ago); allowed in flight: the halo pieces of S(t - 1) and stage h + 3
                     constexpr int j0p = tm1 * HPER < NHW ? tm1 * HPER : NHW, j1p = (tm1 + 1) * HPER < NHW ? (tm1 + 1) * HPER : NHW;
@@ -706,7 +741,7 @@ __device__ __forceinline__ void conv_sk_body(const ConvSkP& p, unsigned char* sm
                 }
                 // the S point's DMA pieces: halo pieces first, then the stage (a later wait for the stage then covers the halo pieces in front of
                 // it), spread over the shadows of the first three MFMAs
-                unit(std::integral_constant<int, 1>{}, [&](auto sc) {
+                half(std::integral_constant<int, 1>{}, [&](auto sc) {
                     constexpr int sidx = decltype(sc)::value;
                     constexpr int j0 = t < TA ? (t * HPER < NHW ? t * HPER : NHW) : 0, j1 = t < TA ? ((t + 1) * HPER < NHW ? (t + 1) * HPER : NHW) : 0;
                     constexpr int nh = j1 - j0;                       // halo pieces of this S point; then PW stage pieces
@@ -737,21 +772,56 @@ __device__ __forceinline__ void conv_sk_body(const ConvSkP& p, unsigned char* sm
         }
         // drain: the reads past the segment's end (garbage, never used) and the DMAs past its end must be gone before the buffers are
         // refilled; the barrier makes that true for every wave's reads
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        // (s_nop: the compiler does not see the MFMA statements, so it cannot keep the distance between the last of them and the first
+        // reader of its result - the layout conversion's stores - itself)
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_nop 15\n\ts_nop 15" ::: "memory");
 #pragma unroll
-        for (int jj = 0; jj < 2; ++jj) {
+        for (int r = 0; r < NA; ++r) asm volatile("" : "+v"(fa[r]));
 #pragma unroll
-            for (int f = 0; f < NF; ++f) asm volatile("" : "+v"(fa[jj][f]));
-            asm volatile("" : "+v"(fb[jj][0]), "+v"(fb[jj][1]));
-        }
+        for (int n = 0; n < 4; ++n) asm volatile("" : "+v"(fb[n]));
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_barrier" ::: "memory");
         SK_STAMP();
-        // the next segment's first halo and stages fly under this segment's epilogue (same row tile: its LDS reads are uncounted inline asm)
+        // Everything behind the K loop - the epilogue, the partial tiles, the finish kernel - works on the 32 x 32 accumulator layout (a lane: one
+        // position x 16 consecutive rows per tile).  Each 32 x 32 block goes through 4 KB of LDS that only this wave touches (no barrier): its four
+        // 16 x 16 tiles in, one f32x16_t out.  The scratch is the wave's 4 KB of the weight ring, dead behind the barrier above.  Row p of the block
+        // (128 bytes: 32 rows of the tile for one position) keeps its 16-byte chunk c at c ^ (p & 7) ^ ((p >> 3) & 1): the stores (8 consecutive
+        // lanes = 8 positions of one chunk) and the loads (ds_read_b128 lane groups) are both free of bank conflicts.
+        f32x16_t acc[NF][2];
+        {
+            // (the addresses are formed HERE, from a lane index the compiler cannot see through: hoisted out of the segment loop they would be six
+            // more registers alive across the K loop, which has none to spare)
+            const int ln = sk_opaque(lane);
+            const int l15 = ln & 15, p31 = ln & 31, ph = ln >> 5;
+            const unsigned sbase = (unsigned)(L::OFF_W + wave * 4096);
+            const unsigned w0 = sbase + (unsigned)(l15 * 128 + ((((ln >> 4) ^ (l15 & 7) ^ (l15 >> 3)) & 7) << 4));      // rows 4 g .. + 3 of the block's upper tile
+            const unsigned w1 = w0 ^ 64u;                                                                                // ... of its lower tile (chunk + 4)
+            const unsigned r0 = sbase + (unsigned)(p31 * 128 + ((((ph << 2) ^ (p31 & 7) ^ ((p31 >> 3) & 1)) & 7) << 4)); // rows 16 hh .. + 3 of position l31
+            const unsigned r1 = r0 ^ 16u, r2 = r0 ^ 32u, r3 = r0 ^ 48u;                                                  // chunks + 1, + 2, + 3
+#pragma unroll
+            for (int f = 0; f < NF; ++f)
+#pragma unroll
+                for (int n = 0; n < 2; ++n) {
+                    asm volatile("ds_write_b128 %0, %1" :: "v"(w0), "v"(c16[2 * f][2 * n]) : "memory");
+                    asm volatile("ds_write_b128 %0, %1 offset:2048" :: "v"(w0), "v"(c16[2 * f][2 * n + 1]) : "memory");
+                    asm volatile("ds_write_b128 %0, %1" :: "v"(w1), "v"(c16[2 * f + 1][2 * n]) : "memory");
+                    asm volatile("ds_write_b128 %0, %1 offset:2048" :: "v"(w1), "v"(c16[2 * f + 1][2 * n + 1]) : "memory");
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    f32x4_t t0, t1, t2, t3;
+                    lds_read16f_asm<0>(t0, r0); lds_read16f_asm<0>(t1, r1); lds_read16f_asm<0>(t2, r2); lds_read16f_asm<0>(t3, r3);
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    asm volatile("" : "+v"(t0), "+v"(t1), "+v"(t2), "+v"(t3));
+                    __builtin_amdgcn_sched_barrier(0);
+                    const f32x8_t lo = __builtin_shufflevector(t0, t1, 0, 1, 2, 3, 4, 5, 6, 7), hi = __builtin_shufflevector(t2, t3, 0, 1, 2, 3, 4, 5, 6, 7);
+                    acc[f][n] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
+                }
+        }
+        // the next segment's first halo and stages fly under this segment's epilogue (same row tile: its LDS reads are uncounted inline asm);
+        // they refill the ring: every wave must have its block out of the scratch first
         const bool same_rt = nxt.ok && (nxt.rt == rt_cur || !L::LDS_TAB);
         const unsigned tab_base = (unsigned)L::OFF_H + bcur;         // (bcur: the buffer behind the last chunk's = where its S points put the tables)
         hb0 = bcur ? 0 : 1;                                          // the next segment starts in the other one
-        if (same_rt) prefetch(nxt);
+        if (same_rt) { asm volatile("s_barrier" ::: "memory"); prefetch(nxt); }
         __builtin_amdgcn_sched_barrier(0);
 
         if (NF != 4 || (cb == 0 && ce == nch)) {                      // (short units are never cut)
@@ -759,7 +829,7 @@ __device__ __forceinline__ void conv_sk_body(const ConvSkP& p, unsigned char* sm
                                                              (cur.rt % RSUB) * (32 * NF));
         } else if constexpr (NF == 4) {
             // raw accumulators, accumulator layout: [wave][f][n][reg / 4][lane][4] fp32 - coalesced 16-byte stores
-            float* pw = p.partial + ((long long)(2 * lid + (cur.first_sk ? 0 : 1))) * L::part_floats() + wave * (128 * 64) + lane * 4;
+            float* pw = p.partial + ((long long)(2 * lid + (cur.first_sk ? 0 : 1))) * L::part_floats() + wave * (128 * 64) + sk_opaque(lane) * 4;
 #pragma unroll
             for (int f = 0; f < 4; ++f)
 #pragma unroll

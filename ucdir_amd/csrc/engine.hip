@@ -44,8 +44,8 @@ struct ConvW {
     bf16_t* Aqkv = nullptr;                              // 1x1 C -> 3C of SelfAttention: fragments of qkv_ws_kernel (qkv_ws.hip.h)
     bf16_t* Atile = nullptr;                             // 3x3: the weight stages of conv3x3_halo_kernel<TM> as contiguous 16 KB blocks (pack_conv_tiled)
     bf16_t* Ask[2] = {nullptr, nullptr}; bf16_t* Ask_up[2] = {nullptr, nullptr};   // 3x3 / Upsample parity classes: stage images of conv_sk_kernel
-    long long sk_up_stride[2] = {0, 0};                  // (pack_conv_sk) for row tiles of 128 ([0]) and 256 rows ([1])
-    bf16_t* Ask1x1 = nullptr;                            // 1x1 (a block's res_conv): one-tap stage image, row tiles of 128: rides in conv1's conv_sk launch
+    long long sk_up_stride[2] = {0, 0};                  // (pack_conv_sk16) for row tiles of 128 ([0]) and 256 rows ([1])
+    bf16_t* Ask1x1 = nullptr;                            // 1x1 (a block's res_conv): one-tap stage image (pack_conv_sk, 32 x 32 fragments), row tiles of 128: rides in conv1's conv_sk launch
 };
 struct AkgmW {
     bf16_t* A = nullptr; float* bias = nullptr; float* Tb = nullptr; float* Tg = nullptr;
@@ -69,11 +69,11 @@ static ConvW upload_conv(DevPool& pool, const float* w, const float* bias, const
     W.rows_pad = P.rows_pad; W.Kpad = P.Kpad; W.ntaps = P.ntaps; W.cin = cin; W.cout = cout;
     if (ks == 3 && cin == 64 && cout == 64 && P.Kpad == 576) W.Aws = pool.upload(pack_conv_ws(P));
     if (ks == 3 && cin % 32 == 0 && P.Kpad == 9 * cin && P.rows_pad % W.TM == 0) W.Atile = pool.upload(pack_conv_tiled(P, W.TM));
-    if (ks == 3 && cin % 32 == 0 && P.Kpad == 9 * cin && cout % 128 == 0) {
-        W.Ask[0] = pool.upload(pack_conv_sk(P.A, 1, P.rows_pad, P.Kpad, cin, 9, 1));
-        if (cout % 256 == 0) W.Ask[1] = pool.upload(pack_conv_sk(P.A, 1, P.rows_pad, P.Kpad, cin, 9, 2));
+    if (ks == 3 && cin % 32 == 0 && cout % 128 == 0) {               // (an odd number of 32-channel chunks too - Kpad = 9 cin + 32 -: conv_sk forced by a test)
+        W.Ask[0] = pool.upload(pack_conv_sk16(P.A, 1, P.rows_pad, P.Kpad, cin, 9, 1));
+        if (cout % 256 == 0) W.Ask[1] = pool.upload(pack_conv_sk16(P.A, 1, P.rows_pad, P.Kpad, cin, 9, 2));
     }
-    if (ks == 1 && cin % 32 == 0 && P.Kpad == cin && cout % 128 == 0 && gamma == nullptr) W.Ask1x1 = pool.upload(pack_conv_sk(P.A, 1, P.rows_pad, P.Kpad, cin, 1, 1));
+    if (ks == 1 && cin % 32 == 0 && cout % 128 == 0 && gamma == nullptr) W.Ask1x1 = pool.upload(pack_conv_sk(P.A, 1, P.rows_pad, P.Kpad, cin, 1, 1));
     if (ks == 1 && cout == 3 * cin && gamma != nullptr && (cin == 256 || cin == 512) && P.Kpad == cin && P.rows_pad >= cout) W.Aqkv = pool.upload(pack_qkv_ws(P, cin));
     return W;
 }
@@ -82,7 +82,7 @@ static void upload_upconv(DevPool& pool, ConvW& W, const float* w, const float* 
     W.Aup = pool.upload(P.A); W.Kup = P.Kpad;
     for (int mw = 1; mw <= 2; ++mw)
         if (W.cin % 32 == 0 && W.cout % (128 * mw) == 0) {
-            std::vector<bf16_t> img = pack_conv_sk(P.A, 4, P.rows_pad, P.Kpad, W.cin, 4, mw);
+            std::vector<bf16_t> img = pack_conv_sk16(P.A, 4, P.rows_pad, P.Kpad, W.cin, 4, mw);
             W.sk_up_stride[mw - 1] = (long long)((img.size() - (size_t)4 * 4 * mw * 2 * 512) / 4);   // (the image ends in four stages of padding)
             W.Ask_up[mw - 1] = pool.upload(img);
         }
@@ -658,7 +658,10 @@ static bool run_conv(const ConvW& w, int mode, ConvCall c, hipStream_t st) {
     if (c.want_stats) {
         p.stats_out = y.stats;
     }
-    if (halo && !c.nchw_out && try_conv_sk(w, c, upph, st)) return c.did_res;
+    // (forced by ucdir_debug_flag("convsk", 1 | 2) the stream-K kernel also takes the 3x3 convs whose tensors are odd multiples of 32 channels, which the
+    // halo kernels below do not: its tests reach one-chunk K loops and a second tensor of one chunk that way; the engine's own choice is as it was)
+    const bool sk_forced = g_convsk.load() > 0 && mode == COLS_S1 && w.ntaps == 9;
+    if ((halo || sk_forced) && !c.nchw_out && try_conv_sk(w, c, upph, st)) return c.did_res;
 
     // ---- which kernel: what rides along and how the grid is cut first, then the kernel that fits ------------------------------------
     int tm_run = w.TM;
@@ -1717,6 +1720,10 @@ int32_t ucdir_debug_launch_plan(const char* what, int32_t wgs, int32_t nchunks, 
             else if (nchunks == 18) ok = conv_sk_strips<1, 8>(wgs, ns, Ws, Wpe, nhp);
             else return -1;
             return ok ? ns * 1000 + nhp : 0;
+        }
+        if (!strcmp(what, "sk_halo_cycles")) {   // conv_sk: LDS cycles of one B fragment read (4 = conflict-free) at row pitch `wgs` of the position space, tap
+            if (wgs < 1 || nchunks < 0 || nchunks > 8 || steps_per_chunk < 0 || steps_per_chunk > 7) return -1;   // `nchunks` (0 .. 8), wave column `steps_per_chunk` (0 .. 7)
+            return sk_halo_read_cycles(wgs, nchunks / 3, nchunks % 3, steps_per_chunk);
         }
     } catch (...) {}
     return -1;

@@ -247,7 +247,8 @@ static inline std::vector<bf16_t> pack_conv_tiled(const PackedConv& P, int TM) {
     return img;
 }
 
-// conv_sk_kernel<MW, NTAPS> (conv_sk.hip.h): every K sub-step's weights as they sit in LDS,
+// The 32 x 32 x 16 stage image of conv_sk.hip.h - today that of the 1x1 res_conv units at the tail of a conv_sk launch (sk_alt_unit); the
+// 3x3 conv and the Upsample classes take pack_conv_sk16 below.  Every K sub-step's weights as they sit in LDS,
 // [parity class][row tile of 128 MW][32-channel chunk c][tap t][fragment f (4 MW)][k16 j (2)][lane 64][8] bf16: lane (hh = lane >> 5,
 // rho = lane & 31) of fragment f holds W[row][t * cin + 32 c + 16 j + 8 hh .. + 7] with row = 32 f + 16 ((rho >> 2) & 1) + (rho & 3) +
 // 4 (rho >> 3): in the 32 x 32 accumulator layout register r of lane half hh is then channel 32 f + 16 hh + r (16 consecutive channels
@@ -271,6 +272,29 @@ static inline std::vector<bf16_t> pack_conv_sk(const std::vector<bf16_t>& A, int
                                 bf16_t* dst = &img[(((((((size_t)par * nrt + rt) * nch + c) * ntaps + t) * nf + f) * 2 + j) * 64 + lane) * 8];
                                 for (int e = 0; e < 8; ++e) dst[e] = src[e];
                             }
+    return img;
+}
+
+// The same stages for the 16 x 16 x 32 K loop of conv_sk_kernel: [parity class][row tile of 128 MW][32-channel chunk c][tap t][fragment R (8 MW)]
+// [lane 64][8] bf16: lane (g = lane >> 4, r = lane & 15) of fragment R holds W[128 MW rt + 16 R + r][t * cin + 32 c + 8 g .. + 7] - rows in their own
+// order: the kernel's layout conversion behind the K loop hands lane half hh of a 32-row fragment f the rows 32 f + 16 hh .. + 15, the
+// 16 consecutive channels per lane that the row permutation of pack_conv_sk gives the 32 x 32 MFMA.  Same sizes as pack_conv_sk: a stage is
+// 8 MW KB of contiguous memory, a fragment 1 KB lane-linear, a 64-row short unit the upper or lower half of a 128-row tile's stage.
+static inline std::vector<bf16_t> pack_conv_sk16(const std::vector<bf16_t>& A, int npar, int rows_pad, int Kld, int cin, int ntaps, int MW) {
+    const int ROWS = 128 * MW, nrt = (rows_pad + ROWS - 1) / ROWS, nch = cin / 32, nf = 8 * MW;
+    std::vector<bf16_t> img((size_t)npar * nrt * nch * ntaps * nf * 512 + (size_t)4 * nf * 512, 0);      // (+ four stages of zeros, as pack_conv_sk)
+    for (int par = 0; par < npar; ++par)
+        for (int rt = 0; rt < nrt; ++rt)
+            for (int c = 0; c < nch; ++c)
+                for (int t = 0; t < ntaps; ++t)
+                    for (int R = 0; R < nf; ++R)
+                        for (int lane = 0; lane < 64; ++lane) {
+                            const int row = rt * ROWS + 16 * R + (lane & 15), g = lane >> 4;
+                            if (row >= rows_pad) continue;
+                            const bf16_t* src = &A[((size_t)par * rows_pad + row) * Kld + (size_t)t * cin + 32 * c + 8 * g];
+                            bf16_t* dst = &img[((((((size_t)par * nrt + rt) * nch + c) * ntaps + t) * nf + R) * 64 + lane) * 8];
+                            for (int e = 0; e < 8; ++e) dst[e] = src[e];
+                        }
     return img;
 }
 
