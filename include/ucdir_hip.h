@@ -83,6 +83,13 @@ void    ucdir_destroy(ucdir_ctx* ctx);
  * convolution, converts to bf16 MFMA layouts and uploads. */
 int32_t ucdir_load_weight(ucdir_ctx* ctx, const char* name, const float* data_host,
                           const int64_t* shape, int32_t ndim);
+/* Invalidates everything made with the previous weights: the captured graphs are dropped and the guide features are stale, so
+ * ucdir_prepare_guide must run again before the next ucdir_unet_forward (which is refused otherwise).  If it fails (a missing
+ * or wrong-sized tensor) the handle refuses ucdir_prepare_guide and forwards with "weights not finalized" until the tensor is
+ * loaded again and a ucdir_finalize_weights succeeds; the planned shape is kept.  (A failed finalise keeps the host copies it
+ * was given; a successful one releases them, so the finalise after it needs every tensor loaded again.  One case differs: a
+ * ucdir_finalize_weights with NO ucdir_load_weight since the last successful one fails with "missing weight" before anything is
+ * released: the graphs are dropped and the handle goes on serving the weights it has.) */
 int32_t ucdir_finalize_weights(ucdir_ctx* ctx);
 /* number of parameter tensors the config expects / the i-th expected name */
 int32_t     ucdir_num_weights(const ucdir_ctx* ctx);
@@ -109,6 +116,11 @@ int32_t ucdir_unet_forward(ucdir_ctx* ctx, const float* cond, const float* x_t,
  * ucdir_amd.diffusion.p_sample_loop does); ~150 launches become one hipGraphLaunch.  Graphs are
  * dropped when weights are re-finalised or the planned shape changes. */
 int32_t ucdir_set_graph(ucdir_ctx* ctx, int32_t on);
+/* What the graph cache did (tests; host-only, launches nothing; additive in ABI 5): out[0] = graphs cached now, out[1..3] =
+ * forwards under ucdir_set_graph(on) that were captured (and launched), replayed from a cached graph, or launched eagerly
+ * (the third different pointer set in a row, see ucdir_set_graph), each since ucdir_create.  Forwards with graphs off or
+ * under ucdir_profile_enable(1) count nowhere.  Returns 0, or -1 on a null argument. */
+int32_t ucdir_debug_graph_stats(const ucdir_ctx* ctx, int32_t out[4]);
 
 /* ---- ancestral sampler update (model/diffusion.py:150-158,171-183), in place on x_t:
  *   x0   = clamp(c_recip * x_t - c_recipm1 * eps, -1, 1)
@@ -357,7 +369,11 @@ int64_t ucdir_workspace_bytes(const ucdir_ctx* ctx);
  * forced (both regardless of the size thresholds: tests), -1 = environment default (UCDIR_NO_CONV_SK; the 4-wave kind).
  * "reuse_acts": 1 = activation buffers are recycled by lifetime at any size, 0 = never, -1 = the default rule (recycled above
  * 512 x 512 compute positions unless UCDIR_KEEP_ACTS is set); a context remembers the mode it planned with and the next
- * ucdir_prepare_guide re-plans (dropping captured graphs) when the mode in force differs.  Unknown names are an error. */
+ * ucdir_prepare_guide re-plans (dropping captured graphs) when the mode in force differs.  Unknown names are an error.
+ * Invalidates the captured graphs and the plan of every handle: a graph holds the kernels the flags chose when it was captured,
+ * so the first ucdir_unet_forward of a handle after any ucdir_debug_flag call drops its graphs and captures again; "flash"
+ * and "reuse_acts" are read when a shape is planned, so the next ucdir_prepare_guide re-plans, and a handle that is not given
+ * one keeps the attention path and buffers it planned (ucdir_amd.ucdir.debug_flag makes every DY3h prepare again). */
 int32_t ucdir_debug_flag(const char* name, int32_t value);
 /* The activation-buffer assignment ucdir_prepare_guide would make for (cfg, B, H, W, pad_mode), callable without a device
  * (tests): one row of six int32 per planned tensor, in planning order: layer index (execution order), which (0 out, 1 h1,

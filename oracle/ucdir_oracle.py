@@ -345,10 +345,11 @@ def _upconv_emu(xb: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, rnd: bool
 
 def dy3h_naive_forward_emu(sd: SD, x: torch.Tensor, level: torch.Tensor, guide: torch.Tensor, prefix: str = "denoise_fn.",
                            taps: Optional[dict] = None, rnd: bool = True, force: Optional[dict] = None,
-                           attn_dtype: str = "bf16") -> torch.Tensor:
+                           attn_dtype: str = "bf16", attn_scores: bool = False) -> torch.Tensor:
     """DY3h.naiveforward (model/ucdir.py:270-293) with bf16 rounding where ucdir_amd/csrc rounds (``rnd=False``: no rounding,
     equal to dy3h_naive_forward up to fp32 re-association).  ``attn_dtype="fp16"``: the attention operands as the engine's
-    ``attn_fp16`` path rounds them (self_attention_emu).
+    ``attn_fp16`` path rounds them (self_attention_emu).  ``attn_scores``: the rounding points of the materialised-score
+    attention path (self_attention_emu ``scores``), which the engine plans where B x query blocks < 32, instead of the flash kernel's.
     ``taps`` and ``force`` only need item assignment, and ``in`` / item lookup: a caller may pass objects that compute a
     metric on assignment and read each forced activation on demand instead of holding every layer at once.
     ``force`` (teacher forcing, for per-layer checks): {tap name: tensor}.  After a layer's own output has been recorded in ``taps``,
@@ -367,7 +368,7 @@ def dy3h_naive_forward_emu(sd: SD, x: torch.Tensor, level: torch.Tensor, guide: 
     def run_block(base, srcs):
         y = resblock_dy3h_emu(sd, base + "res_block.", srcs, temb, guide, rnd, taps, force)
         if (base + "attn.qkv.weight") in sd:
-            y = self_attention_emu(sd, base + "attn.", y, rnd, attn_dtype)
+            y = self_attention_emu(sd, base + "attn.", y, rnd, attn_dtype, scores=attn_scores)
         return forced(base[:-1], y)
 
     for kind, base in downs:

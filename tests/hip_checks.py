@@ -155,14 +155,14 @@ class debug_flags:
         self.flags = flags
 
     def __enter__(self):
-        L = ulib.load()
+        from ucdir_amd.ucdir import debug_flag       # (a DY3h that holds a plan prepares and plans again under the flags)
         for k, v in self.flags.items():
-            ulib.check(L.ucdir_debug_flag(k.encode(), v))
+            debug_flag(k, v)
 
     def __exit__(self, *exc):
-        L = ulib.load()
+        from ucdir_amd.ucdir import debug_flag
         for k in self.flags:
-            ulib.check(L.ucdir_debug_flag(k.encode(), 0 if k == "persist_grid" else -1))
+            debug_flag(k, 0 if k == "persist_grid" else -1)
 
 
 def rng(seed):
@@ -375,6 +375,7 @@ def attention_case(B, C, H, W, seed=0, fp16=False, flash=1):
     dy = torch.empty(B, C, H, W, device=DEV)
     n = lambda k: sd[k].numpy().copy()
     dx = x.to(DEV)
+    # (straight at the library: the ucdir_op_* entry point reads the flag when it runs and no DY3h is involved; a DY3h that holds a plan needs ucdir_amd.ucdir.debug_flag, as hip_checks.debug_flags does)
     ulib.check(L.ucdir_debug_flag(b"flash", flash))
     try:
         ulib.check(L.ucdir_op_attention(_p(dx), B, C, H, W, _hp(n("a.norm.weight")), _hp(n("a.norm.bias")),
@@ -510,6 +511,7 @@ def attention_emu_case(B, C, H, W, seed=0, fp16=False, flash=1, masking=False, u
     def run():
         ulib.check(L.ucdir_op_attention(_p(dx), B, C, H, W, *[_hp(a) for a in hp], int(fp16), _p(dy), _st()))
         torch.cuda.synchronize()
+    # (straight at the library: the ucdir_op_* entry point reads the flag when it runs and no DY3h is involved; a DY3h that holds a plan needs ucdir_amd.ucdir.debug_flag, as hip_checks.debug_flags does)
     ulib.check(L.ucdir_debug_flag(b"flash", flash))
     try:
         _, keys = profile_keys(L, run)
@@ -567,18 +569,19 @@ class HipLayers:
                 self.controls_out[name] = metrics(self.controls[name](self[key]), bfr(y))
 
 
-def layerwise_emu_sample(dn, sd, x6, lvl, guide, b, pad, attn_dtype="bf16", controls=None, eps=None):
+def layerwise_emu_sample(dn, sd, x6, lvl, guide, b, pad, attn_dtype="bf16", controls=None, eps=None, attn_scores=False):
     """Layer-wise metrics of sample ``b`` of the LAST forward of ``dn`` (x6, lvl, guide: that forward's host inputs; ``pad``:
     the forward reflect-padded them by pad32 like forward_split, else they are already multiples of 32) against the emulation
     fed with the HIP path's own activations.  Returns {layer or layer:h1: metrics}; with ``controls`` (HipLayers) the pair
     ({layer: metrics}, {controlled layer: metrics of the wrong copy}).  ``eps``: that forward's output (B, 3, H, W); adds
-    "eps" = the final conv on the HIP path's last activation (cropped like the forward's) against it."""
+    "eps" = the final conv on the HIP path's last activation (cropped like the forward's) against it.  ``attn_scores``: the
+    forward took the materialised-score attention path (oracle.dy3h_naive_forward_emu)."""
     xs, gs = x6[b:b + 1], guide[b:b + 1]
     if pad:
         ph, pw = O.pad32(x6.shape[-2]), O.pad32(x6.shape[-1])
         xs, gs = F.pad(xs, (0, pw, 0, ph), mode="reflect"), F.pad(gs, (0, pw, 0, ph), mode="reflect")
     hl = HipLayers(dn, b, controls=controls)
-    e = O.dy3h_naive_forward_emu(sd, xs, lvl[b:b + 1], gs, taps=hl, force=hl, attn_dtype=attn_dtype)
+    e = O.dy3h_naive_forward_emu(sd, xs, lvl[b:b + 1], gs, taps=hl, force=hl, attn_dtype=attn_dtype, attn_scores=attn_scores)
     if eps is not None:
         hl.out["eps"] = metrics(eps[b:b + 1], e[..., :x6.shape[-2], :x6.shape[-1]])
     return (hl.out, hl.controls_out) if controls is not None else hl.out
@@ -774,7 +777,7 @@ class emu_float64_sums:
         O.F, O.torch = self._saved
 
 
-def emu_self_comparison(sd, cfg, B, H, W, levels, seed, inputs=None):
+def emu_self_comparison(sd, cfg, B, H, W, levels, seed, inputs=None, attn_scores=False):
     """Two summation orders of the emulation on the same inputs, layer by layer as layerwise_emu_case compares the HIP path with
     it: one forward stores its activations as bf16; then every layer is evaluated on those stored activations (teacher forcing)
     once with torch's fp32 sums - the role of the HIP path - and once with float64 sums.  {activation | "eps": metrics}.
@@ -783,12 +786,12 @@ def emu_self_comparison(sd, cfg, B, H, W, levels, seed, inputs=None):
     lvl = torch.tensor(levels, dtype=torch.float32).view(B, 1)
     x6 = torch.cat([cond, x_t], 1)
     first = {}
-    O.dy3h_naive_forward_emu(sd, x6, lvl, guide, taps=first)
+    O.dy3h_naive_forward_emu(sd, x6, lvl, guide, taps=first, attn_scores=attn_scores)
     force = {k: bfr(v) for k, v in first.items()}
     t32, t64 = {}, {}
-    e32 = O.dy3h_naive_forward_emu(sd, x6, lvl, guide, taps=t32, force=force)
+    e32 = O.dy3h_naive_forward_emu(sd, x6, lvl, guide, taps=t32, force=force, attn_scores=attn_scores)
     with emu_float64_sums():
-        e64 = O.dy3h_naive_forward_emu(sd, x6, lvl, guide, taps=t64, force=force)
+        e64 = O.dy3h_naive_forward_emu(sd, x6, lvl, guide, taps=t64, force=force, attn_scores=attn_scores)
     out = {"eps": metrics(e32, e64)}
     for k in force:
         out[k[len("denoise_fn."):]] = metrics(bfr(t32[k]), bfr(t64[k]))

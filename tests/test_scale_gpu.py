@@ -77,6 +77,7 @@ def test_flash_attention_online_softmax_rescale_is_exercised():
     outs = {}
     try:
         for flash in (1, 0):
+            # (straight at the library: the ucdir_op_* entry point reads the flag when it runs and no DY3h is involved; a DY3h that holds a plan needs ucdir_amd.ucdir.debug_flag, as hip_checks.debug_flags does)
             C.ulib.check(L.ucdir_debug_flag(b"flash", flash))
             dy = torch.empty(B, Cc, H, W, device="cuda")
             C.ulib.check(L.ucdir_op_attention(C._p(dx), B, Cc, H, W, C._hp(n("a.norm.weight")), C._hp(n("a.norm.bias")),

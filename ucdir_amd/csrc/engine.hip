@@ -375,6 +375,7 @@ static void launch_halo(GemmP p, hipStream_t st) {
 }
 
 // compute units of the current device (persistent kernels launch one workgroup per CU)
+static std::atomic<unsigned> g_flag_epoch{0};   // bumped by every ucdir_debug_flag: a captured graph holds the kernels the flags chose at capture (forward_graph compares)
 static std::atomic<int> g_persist_grid{0};     // > 0: ucdir_debug_flag("persist_grid", n) forces the grid of the persistent kernels (tests: many tiles per workgroup on small inputs)
 static int num_cus() {
     if (g_persist_grid > 0) return g_persist_grid;
@@ -1146,6 +1147,7 @@ struct ucdir_ctx {
     float* tcbuf = nullptr;             // AKGM fold-table scratch [B][9][8 * max C] (akgm_tc_kernel)
     bool guide_ready = false;
     bool acts_reused = false;           // plan_shapes recycled activation buffers by lifetime: no debug_read
+    unsigned plan_epoch = 0;            // g_flag_epoch the shape was planned under ("flash" decides the attention buffers of a plan)
     double flops = 0;
     // HIP-graph replay of one forward (B = 1 / -p val latency path): captured once per (cond, x_t, level, eps) pointer
     // set on a library-owned stream, replayed on the caller's stream.  Dropped whenever weights or shapes change.
@@ -1155,6 +1157,8 @@ struct ucdir_ctx {
     hipStream_t cap_stream = nullptr;
     int miss_streak = 0;                                   // consecutive forwards whose pointer set was not cached
     const void* last_miss[4] = {nullptr, nullptr, nullptr, nullptr};
+    unsigned flag_epoch = 0;                               // g_flag_epoch the cached graphs were captured under
+    int n_capture = 0, n_replay = 0, n_eager = 0;          // forwards under use_graph since creation (ucdir_debug_graph_stats)
     float* splitk = nullptr;                               // this context's split-K scratch (two handles on two streams of one device do not share partial sums)
     void drop_graphs() {
         for (auto& f : graphs) { (void)hipGraphExecDestroy(f.ex); (void)hipGraphDestroy(f.g); }
@@ -1196,6 +1200,11 @@ static const std::vector<float>& W_(ucdir_ctx* c, const std::string& name, size_
 static void finalize_weights(ucdir_ctx* c) {
     const auto& cfg = c->cfg;
     const int inner = cfg.inner_channel;
+    // nothing made with the old weights outlives them: a finalise that throws half way (a tensor of the wrong size) leaves a
+    // handle that refuses forwards until a finalise succeeds, and the guide features rt[].G (made with the old lw[].gw) need a
+    // new ucdir_prepare_guide either way
+    c->finalized = false;
+    c->guide_ready = false;
     c->wpool.release();
     c->lw.assign(c->layers.size(), LayerW());
     c->mlp_w1 = c->wpool.upload(W_(c, "noise_level_mlp.1.weight", (size_t)4 * inner * inner));
@@ -1374,6 +1383,7 @@ static void plan_shapes(ucdir_ctx* c, int B, int H, int W, int pad_mode) {
     c->B = B; c->H = H; c->W = W; c->pad_mode = pad_mode;
     c->Hc = Hc; c->Wc = Wc;
     c->acts_reused = reuse;
+    c->plan_epoch = g_flag_epoch.load();
     std::vector<bf16_t*> bufs;                   // by id; an id's buffer is allocated (zeroed) where the plan first uses it
     int maxN = 0, attC = 0;
     double fl = 0;
@@ -1495,15 +1505,18 @@ static void forward(ucdir_ctx* c, const float* cond, const float* xt, const floa
 // buffers) and replayed: ~150 kernel launches become one hipGraphLaunch.  Capture runs on a library-owned stream (the
 // legacy default stream cannot be captured); nothing on the launch path allocates or synchronises.
 static void forward_graph(ucdir_ctx* c, const float* cond, const float* xt, const float* level, float* eps, hipStream_t st) {
+    // the kernels of a captured forward are those the debug flags chose at capture: a flag set since then drops the graphs
+    const unsigned epoch = g_flag_epoch.load();
+    if (epoch != c->flag_epoch) { c->drop_graphs(); c->flag_epoch = epoch; }
     for (auto& f : c->graphs)
-        if (f.cond == cond && f.xt == xt && f.lvl == level && f.eps == eps) { c->miss_streak = 0; HIPC(hipGraphLaunch(f.ex, st)); return; }
+        if (f.cond == cond && f.xt == xt && f.lvl == level && f.eps == eps) { c->miss_streak = 0; HIPC(hipGraphLaunch(f.ex, st)); ++c->n_replay; return; }
     // Miss.  Callers with persistent buffers (p_sample_loop) miss once per buffer set; callers that hand over fresh tensors
     // every step (p_sample, the ddim / dpm-solver samplers) would re-capture and re-instantiate a ~150-node graph - plus a
     // stream synchronisation - on every forward: after two misses in a row a pointer set is launched eagerly unless it is
     // the very set that missed last time (then it IS persistent and worth a capture).
     const bool same_as_last = c->last_miss[0] == cond && c->last_miss[1] == xt && c->last_miss[2] == level && c->last_miss[3] == eps;
     c->last_miss[0] = cond; c->last_miss[1] = xt; c->last_miss[2] = level; c->last_miss[3] = eps;
-    if (c->miss_streak >= 2 && !same_as_last) { ++c->miss_streak; forward(c, cond, xt, level, eps, st); return; }
+    if (c->miss_streak >= 2 && !same_as_last) { ++c->miss_streak; forward(c, cond, xt, level, eps, st); ++c->n_eager; return; }
     ++c->miss_streak;
     if (c->graphs.size() >= 8) { const int ms = c->miss_streak; c->drop_graphs(); c->miss_streak = ms; }   // bounded cache
     if (!c->cap_stream) HIPC(hipStreamCreateWithFlags(&c->cap_stream, hipStreamNonBlocking));
@@ -1519,6 +1532,7 @@ static void forward_graph(ucdir_ctx* c, const float* cond, const float* xt, cons
     }
     c->graphs.push_back(f);
     HIPC(hipGraphLaunch(f.ex, st));
+    ++c->n_capture;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1589,9 +1603,11 @@ int32_t ucdir_prepare_guide(ucdir_ctx* ctx, const float* guide, int32_t B, int32
     require(ctx->finalized, "weights not finalized");
     DevGuard dg(ctx->cfg.device);
     hipStream_t st = (hipStream_t)stream;
-    // (a plan made under another "reuse_acts" mode is as stale as one of another shape)
+    // (a plan made under another "reuse_acts" mode, or before the latest ucdir_debug_flag call - "flash" picks the attention
+    // path and its buffers when a shape is planned -, is as stale as one of another shape)
     if (B != ctx->B || H != ctx->H || W != ctx->W || pad_mode != ctx->pad_mode || ctx->rt.empty() ||
-        reuse_acts_mode(g_reuse_acts, ctx->Hc, ctx->Wc) != ctx->acts_reused) {
+        reuse_acts_mode(g_reuse_acts, ctx->Hc, ctx->Wc) != ctx->acts_reused || ctx->plan_epoch != g_flag_epoch.load()) {
+        { int hc, wc; plan_compute_size(ctx->cfg, B, H, W, pad_mode, hc, wc); }   // a refused shape keeps the plan AND its graphs
         HIPC(hipStreamSynchronize(st));
         ctx->drop_graphs();
         plan_shapes(ctx, B, H, W, pad_mode);
@@ -1618,6 +1634,9 @@ int32_t ucdir_unet_forward(ucdir_ctx* ctx, const float* cond, const float* x_t, 
             "ucdir_unet_forward: (B,H,W) = (" + std::to_string(B) + "," + std::to_string(H) + "," + std::to_string(W) +
             ") does not match the shape planned by ucdir_prepare_guide (" + std::to_string(ctx->B) + "," +
             std::to_string(ctx->H) + "," + std::to_string(ctx->W) + ")");
+    // refused before the graph cache sees the pointer set: a refused call leaves the miss policy where it was
+    require(ctx->finalized, "weights not finalized");
+    require(ctx->guide_ready, "ucdir_prepare_guide must be called before ucdir_unet_forward");
     DevGuard dg(ctx->cfg.device);
     hipStream_t st = (hipStream_t)stream;
     if (ctx->use_graph && !g_prof.on) forward_graph(ctx, cond, x_t, noise_level, eps, st);
@@ -1647,6 +1666,13 @@ int32_t ucdir_set_graph(ucdir_ctx* ctx, int32_t on) {
     ctx->use_graph = on != 0;
     if (!on) ctx->drop_graphs();
     API_END
+}
+
+int32_t ucdir_debug_graph_stats(const ucdir_ctx* ctx, int32_t out[4]) {
+    // pure host reads (nothing is launched): graphs cached now; captures, replays and eager launches under use_graph since creation
+    if (!ctx || !out) { fail("null argument"); return -1; }
+    out[0] = (int32_t)ctx->graphs.size(); out[1] = ctx->n_capture; out[2] = ctx->n_replay; out[3] = ctx->n_eager;
+    return 0;
 }
 
 int32_t ucdir_debug_read(ucdir_ctx* ctx, const char* layer, const char* what, float* dst, int64_t dst_elems, void* stream) {
@@ -1695,6 +1721,7 @@ int32_t ucdir_debug_flag(const char* name, int32_t value) {
     else if (!strcmp(name, "persist_grid")) g_persist_grid = value;   // persistent kernels: workgroups per launch (0 = one per CU)
     else if (!strcmp(name, "reuse_acts")) g_reuse_acts = value < 0 ? -1 : value != 0;   // activation buffers recycled by lifetime: 1 at any size, 0 never, -1 UCDIR_KEEP_ACTS + the 512^2 threshold; the next ucdir_prepare_guide re-plans
     else throw std::runtime_error(std::string("unknown debug flag ") + name);
+    ++g_flag_epoch;
     API_END
 }
 

@@ -38,6 +38,7 @@ _SIGS = {
     "ucdir_prepare_guide": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "ucdir_unet_forward": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "ucdir_set_graph": (c_int32, [c_void_p, c_int32]),
+    "ucdir_debug_graph_stats": (c_int32, [c_void_p, POINTER(c_int32)]),
     "ucdir_sampler_step_rng": (c_int32, [c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_float,
                                          ctypes.c_uint64, ctypes.c_uint32, c_void_p]),
     "ucdir_fill_normal": (c_int32, [c_void_p, c_int64, ctypes.c_uint64, ctypes.c_uint32, c_void_p]),

@@ -105,6 +105,17 @@ def debug_act_plan(cfg: UNetConfig, B, H, W, pad_mode=1, reuse=-1):
             for i in range(n)]
 
 
+_FLAG_EPOCH = [0]        # bumped by debug_flag: part of every DY3h's guide key, so the forward after a flag change prepares (and plans) again
+
+
+def debug_flag(name, value):
+    """Tests: ``ucdir_debug_flag(name, value)`` (process-wide).  "flash" and "reuse_acts" are read when a shape is planned: every
+    DY3h prepares its guide again - and the engine re-plans - on its first forward after a call, so the flag is in force from
+    that forward on, as it is for a handle created after the call."""
+    _lib.check(_lib.load().ucdir_debug_flag(name.encode() if isinstance(name, str) else name, int(value)))
+    _FLAG_EPOCH[0] += 1
+
+
 class DY3h(nn.Module):
     """Conditional UNet denoiser; same signature as the reference's ``DY3h`` (model/ucdir.py:204-207)."""
 
@@ -225,11 +236,18 @@ class DY3h(nn.Module):
         if self._h is not None:
             _lib.check(_lib.load().ucdir_set_graph(self._h, 1 if on else 0))
 
+    def graph_stats(self):
+        """Tests: ``ucdir_debug_graph_stats`` as a dict - ``cached`` graphs now; ``captures``, ``replays`` and ``eager`` launches
+        under ``set_graph(True)`` since the engine handle was created (all 0 before the first forward).  Launches nothing."""
+        out = (ctypes.c_int32 * 4)()
+        if self._h is not None and _lib.load().ucdir_debug_graph_stats(self._h, out) != 0:
+            raise _lib.UcdirError(_lib.load().ucdir_last_error().decode())
+        return dict(zip(("cached", "captures", "replays", "eager"), (int(v) for v in out)))
+
     def set_reuse_acts(self, mode=-1):
         """Tests: ``ucdir_debug_flag("reuse_acts")`` - 1 recycles activation buffers by lifetime at any size, 0 never, -1 the
         default rule.  The flag is process-wide; this module's next forward re-plans under it."""
-        _lib.check(_lib.load().ucdir_debug_flag(b"reuse_acts", int(mode)))
-        self._gkey = None
+        debug_flag("reuse_acts", mode)
 
     def _dev(self):
         return torch.device("cuda", self._device_index())
@@ -241,7 +259,7 @@ class DY3h(nn.Module):
 
     def prepare_guide(self, guide, pad_mode=1):
         L = _lib.load()
-        key = (guide.data_ptr(), guide._version, tuple(guide.shape), tuple(guide.stride()), pad_mode)
+        key = (guide.data_ptr(), guide._version, tuple(guide.shape), tuple(guide.stride()), pad_mode, _FLAG_EPOCH[0])
         if key != self._gkey and not self._sig_hold and not self._wdirty and self._wsig != self._weights_signature():
             self._wdirty = True                 # a parameter was updated in place since the engine packed the weights
         self._sync_weights()
