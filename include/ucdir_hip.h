@@ -166,6 +166,33 @@ int32_t ucdir_fewstep_update(float* x, const float* eps, float* m_prev, const fl
 int32_t ucdir_fewstep_update_batched(float* x, const float* eps, float* m_prev, const float* noise, int64_t n, int64_t per,
                                      float c_recip, float c_recipm1, int32_t flags, float p, float q, float r, float b1, int32_t store_m,
                                      float sigma, const uint64_t* seeds_dev, uint32_t step, void* stream);
+/* x0 thresholding of DPM-Solver++ (additive in ABI 5).  ucdir_fewstep_update_thresholded is ucdir_fewstep_update_batched with one
+ * more step between x0 and its uses: sample b (n / per samples of `per` elements, per a multiple of 4, n a whole number of them)
+ *   x0 <- min(max(x0, -s_dev[b]), s_dev[b])         (torch.clamp: a NaN x0 stays NaN, a NaN s_dev[b] makes the sample NaN)
+ *   x0 <- x0 / s_dev[b]                             (when divide != 0; correctly rounded fp32 division)
+ * and that x0 enters p * x0 and is stored in m_prev.  seeds_dev may be NULL: one stream of `seed` over the whole buffer, as
+ * ucdir_fewstep_update draws it.  flags & 1 (the clamp to [-1, 1]) is refused.  s_dev: n / per floats on the device of x, 4-byte
+ * aligned.  Static thresholding is s_dev[b] = max_val with divide = 0.
+ *
+ * ucdir_fewstep_threshold writes the dynamic threshold (Imagen; correcting_x0_fn = "dynamic_thresholding" of the DPM-Solver
+ * package) of every sample into s_dev.  With x0_i = c_recip * (x_i - c_recipm1 * eps_i) - the factored form of the update, every
+ * operation rounded on its own - and A = the `per` values |x0_i| of the sample in ascending order of their bit patterns (-0 is 0,
+ * inf above every finite value, NaN above inf):
+ *   pos = ratio * (per - 1) in float64, lo = floor(pos), hi = min(lo + 1, per - 1), w = pos - lo
+ *   q   = A[lo] when A[lo] == A[hi], else fl32(A[lo] + w * (A[hi] - A[lo])) evaluated in float64; NaN when the sample holds a NaN
+ *   s_dev[b] = max(q, max_val), NaN when q is
+ * A[lo] and A[hi] are selected exactly (radix selection on integer counts): s_dev is bit-identical from run to run and the value
+ * of a sample does not depend on the other samples of the buffer.  x and eps are only read.  workspace: at least
+ * ucdir_fewstep_threshold_workspace_bytes(n / per) bytes (a host query; -1 for a negative count) on the device of x, 16-byte
+ * aligned like x and eps, contents arbitrary: the call zeroes what it uses.  ratio in [0, 1], max_val > 0, per below 2^31, at
+ * most 65535 samples.  Neither call synchronises or allocates: both can be captured in a graph. */
+int32_t ucdir_fewstep_update_thresholded(float* x, const float* eps, float* m_prev, const float* noise, int64_t n, int64_t per,
+                                         float c_recip, float c_recipm1, int32_t flags, float p, float q, float r, float b1,
+                                         int32_t store_m, float sigma, uint64_t seed, const uint64_t* seeds_dev, uint32_t step,
+                                         const float* s_dev, int32_t divide, void* stream);
+int64_t ucdir_fewstep_threshold_workspace_bytes(int64_t nsamples);
+int32_t ucdir_fewstep_threshold(const float* x, const float* eps, int64_t n, int64_t per, float c_recip, float c_recipm1,
+                                double ratio, float max_val, float* s_dev, void* workspace, int64_t workspace_bytes, void* stream);
 /* Window batch of the inter-step patch split (utils/util.py:113-137: F.pad(..., mode='reflect') then one slice per window) in ONE launch,
  * straight from the un-padded canvas: out[(w * B + b)][c][y][x] = x[b][c][refl(h0_w + y - pad)][refl(w0_w + x - pad)], x (B, C, H, W) fp32,
  * out (nwin * B, C, skip, skip) fp32, win_dev = nwin pairs (h0, w0) of int32 ON THE DEVICE in padded coordinates (the window list of

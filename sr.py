@@ -53,12 +53,18 @@ def make_val_dataset(val_opt, decode_device="cpu"):
 
 
 def apply_sampler_flags(opt, args):
-    """--sampler / --sampler-steps / --sampler-order / --ddim-eta override the keys of model.sampler (DDPM.__init__ reads it)."""
+    """--sampler / --sampler-steps / --sampler-order / --ddim-eta override the keys of model.sampler (DDPM.__init__ reads it);
+    --sampler-threshold / --sampler-threshold-max / --sampler-threshold-ratio those of its ``thresholding`` mapping."""
     over = {"name": args.sampler, "steps": args.sampler_steps, "order": args.sampler_order, "eta": args.ddim_eta}
     over = {k: v for k, v in over.items() if v is not None}
-    if over:
+    thr = {"kind": args.sampler_threshold, "max_val": args.sampler_threshold_max, "ratio": args.sampler_threshold_ratio}
+    thr = {k: v for k, v in thr.items() if v is not None}
+    if over or thr:
         spec = dict(opt["model"].get("sampler") or {})
         spec.update(over)
+        if thr:
+            was = spec.get("thresholding")
+            spec["thresholding"] = dict({"kind": was} if isinstance(was, str) else (was or {}), **thr)
         opt["model"]["sampler"] = spec
     return opt
 
@@ -102,6 +108,10 @@ def make_parser():
     parser.add_argument("--sampler-steps", type=int, default=None, help="network calls of a ddim / dpm_solver++ restoration")
     parser.add_argument("--sampler-order", type=int, choices=[1, 2], default=None, help="dpm_solver++ multistep order")
     parser.add_argument("--ddim-eta", type=float, default=None, help="ddim noise scale (0: deterministic, 1: the reference's setting)")
+    parser.add_argument("--sampler-threshold", choices=["none", "static", "dynamic"], default=None,
+                        help="dpm_solver++ x0 correction: clamp to +-max (static) or Imagen's dynamic thresholding (per-image quantile)")
+    parser.add_argument("--sampler-threshold-max", type=float, default=None, help="max value of the x0 correction (default 1)")
+    parser.add_argument("--sampler-threshold-ratio", type=float, default=None, help="quantile of dynamic thresholding (default 0.995)")
     parser.add_argument("--metrics-device", choices=["cpu", "gpu"], default="cpu",
                         help="score PSNR / SSIM on the host (numpy / scipy) or on the GPU (HIP kernel, the same uint8 images)")
     parser.add_argument("--jpeg-device", choices=["cpu", "gpu"], default="cpu",

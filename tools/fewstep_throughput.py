@@ -1,14 +1,18 @@
 """Throughput of the few-step samplers against the 50-step ancestral sampler, on the flagship configuration of bench.py (full SID
 UNet, synthetic weights, T = 50, linear_end 0.4):
 
-    python tools/fewstep_throughput.py [--steps K] [--warmup W] [--configs ddim-5,dpm_solver++-20] [--no-patch]
+    python tools/fewstep_throughput.py [--steps K] [--warmup W] [--configs ddim-5,dpm_solver++-20] [--no-patch] [--thresholding]
 
 prints ONE JSON line: restored images/s at B = 16, 256^2 (the UNet computes at 288^2) for ddpm-50 (cross-check against bench.py),
 ddim-5/10/25 and dpm_solver++-10/20, and seconds per image for the full-resolution 1424 x 2128 image through the inter-step patch
 split (DDPM.test's reflect pad 64, one GPU) at ddpm-50 and dpm_solver++-20.  Times are wall-clock around whole restorations
 (predictor + sampler) after a synchronize; each restoration draws its noise in-kernel.  With synthetic weights the restored images
 mean nothing: this measures cost, not quality ("finite_fraction": the random network is no noise predictor, and DPM-Solver++'s
-unclipped x0 = (x - sigma eps) / alpha can run away to inf on it - the work per call is the same)."""
+unclipped x0 = (x - sigma eps) / alpha can run away to inf on it - the work per call is the same).
+
+``--thresholding`` adds, in the same run, dpm_solver++-20 with static and with dynamic x0 thresholding (tags
+``dpm_solver++-20:static`` / ``:dynamic``) and a ``ms_per_call`` entry (restoration time / network calls) for them and the
+unthresholded dpm_solver++-20 row they are read against."""
 import argparse
 import json
 import os
@@ -22,13 +26,18 @@ sys.path.insert(0, ROOT)
 
 CONFIGS = ("ddpm-50", "ddim-5", "ddim-10", "ddim-25", "dpm_solver++-10", "dpm_solver++-20")
 PATCH_CONFIGS = ("ddpm-50", "dpm_solver++-20")
+THRESHOLD_BASE = "dpm_solver++-20"
 
 
 def sampler_of(tag):
+    tag, _, kind = tag.partition(":")
     name, steps = tag.rsplit("-", 1)
     if name == "ddpm":
         return None
-    return {"sampler": name, "steps": int(steps), "order": 2, "eta": 1.0, "time_input": "level"}
+    out = {"sampler": name, "steps": int(steps), "order": 2, "eta": 1.0, "time_input": "level"}
+    if kind:
+        out["thresholding"] = {"kind": kind, "max_val": 1.0, "ratio": 0.995}
+    return out
 
 
 def timed(net, x, tag, steps, warmup):
@@ -54,6 +63,7 @@ def main():
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--configs", default=",".join(CONFIGS))
     ap.add_argument("--no-patch", action="store_true", help="skip the full-resolution patch-split leg")
+    ap.add_argument("--thresholding", action="store_true", help="add dpm_solver++-20 with static and dynamic x0 thresholding")
     args = ap.parse_args()
     import torch.nn.functional as F
     from bench import sid_opt
@@ -71,9 +81,15 @@ def main():
     rec = {"metric": "few-step samplers: restored images/s at B=%d, %dx%d SID; s/image full-resolution patch split" % (B, S, S),
            "batch": B, "size": S, "steps": args.steps, "warmup": args.warmup, "data": "synthetic weights (cost only, not quality)",
            "img_per_s": {}, "patch_s_per_image": {}, "finite_fraction": {}}
-    for tag in args.configs.split(","):
+    tags = args.configs.split(",")
+    if args.thresholding:
+        tags = [t for t in tags if t != THRESHOLD_BASE] + [THRESHOLD_BASE, THRESHOLD_BASE + ":static", THRESHOLD_BASE + ":dynamic"]
+        rec["ms_per_call"] = {}
+    for tag in tags:
         dt, rec["finite_fraction"][tag] = timed(net, cond, tag, args.steps, args.warmup)
         rec["img_per_s"][tag] = B / dt
+        if args.thresholding and tag.startswith(THRESHOLD_BASE):
+            rec["ms_per_call"][tag] = 1e3 * dt / sampler_of(tag)["steps"]
     if not args.no_patch:
         H, W = 1424, 2128
         img = torch.from_numpy(synth_inputs(1, H, W, seed=0)[0]).to(dev)

@@ -72,25 +72,33 @@ int32_t ucdir_fill_normal_batched(float* x, int64_t n, int64_t per, const uint64
     API_END
 }
 
-// the few-step samplers' fused update (csrc/fewstep.hip.h); seeds_dev == nullptr: one stream of `seed` over the whole buffer
+// the few-step samplers' fused update (csrc/fewstep.hip.h); seeds_dev == nullptr: one stream of `seed` over the whole buffer;
+// s_dev != nullptr: sample b thresholds its x0 by s_dev[b]
 static void fewstep_launch(const char* who, float* x, const float* eps, float* m_prev, const float* noise, int64_t n, int64_t per,
-                           const FewstepCoef& k, uint64_t seed, const uint64_t* seeds_dev, uint32_t step, void* stream) {
+                           const FewstepCoef& k, uint64_t seed, const uint64_t* seeds_dev, uint32_t step, void* stream,
+                           const float* s_dev = nullptr, int32_t divide = 0) {
     const std::string w(who);
     require(x && eps, w + ": null argument");
     require(n >= 0, w + ": negative element count");
     require(m_prev || (k.b1 == 0.f && !k.store_m), w + ": m_prev is needed when b1 != 0 or store_m is set");
-    const void* others[4] = {eps, m_prev, noise, seeds_dev};
-    const char* names[4] = {"eps", "m_prev", "noise", "seeds"};
-    const int device = same_device(w, x, "x", others, names, 4);
+    const void* others[5] = {eps, m_prev, noise, seeds_dev, s_dev};
+    const char* names[5] = {"eps", "m_prev", "noise", "seeds", "s_dev"};
+    const int device = same_device(w, x, "x", others, names, 5);
     for (const void* q : {(const void*)x, (const void*)eps, (const void*)m_prev, (const void*)noise})
         require(((uintptr_t)q & 15) == 0, w + ": buffers must be 16-byte aligned");
-    if (seeds_dev)
+    require(((uintptr_t)s_dev & 3) == 0, w + ": s_dev must be 4-byte aligned");
+    if (seeds_dev || s_dev)
         require(per > 0 && per % 4 == 0 && n % per == 0, w + ": n must be a whole number of samples of `per` elements, per a multiple of 4");
     if (n == 0) return;
     DevGuard dg(device);
     long long blocks = ((n + 3) / 4 + 255) / 256; if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(fewstep_update_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, eps, m_prev, noise, (long long)n, k,
-                       (unsigned long long)seed, step, (const unsigned long long*)seeds_dev, (long long)(per / 4));
+    if (s_dev)
+        hipLaunchKernelGGL(fewstep_update_thresholded_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, eps, m_prev, noise,
+                           (long long)n, k, (unsigned long long)seed, step, (const unsigned long long*)seeds_dev, (long long)(per / 4), s_dev,
+                           (int)divide);
+    else
+        hipLaunchKernelGGL(fewstep_update_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, eps, m_prev, noise, (long long)n, k,
+                           (unsigned long long)seed, step, (const unsigned long long*)seeds_dev, (long long)(per / 4));
     HIPC(hipGetLastError());
 }
 
@@ -112,6 +120,64 @@ int32_t ucdir_fewstep_update_batched(float* x, const float* eps, float* m_prev, 
     require((flags & ~(FEWSTEP_CLIP | FEWSTEP_FACTORED)) == 0, "fewstep update: unknown flags");
     const FewstepCoef k{c_recip, c_recipm1, p, q, r, b1, sigma, flags, store_m != 0};
     fewstep_launch("ucdir_fewstep_update_batched", x, eps, m_prev, noise, n, per, k, 0, seeds_dev, step, stream);
+    API_END
+}
+
+int32_t ucdir_fewstep_update_thresholded(float* x, const float* eps, float* m_prev, const float* noise, int64_t n, int64_t per, float c_recip,
+                                         float c_recipm1, int32_t flags, float p, float q, float r, float b1, int32_t store_m, float sigma,
+                                         uint64_t seed, const uint64_t* seeds_dev, uint32_t step, const float* s_dev, int32_t divide,
+                                         void* stream) {
+    API_BEGIN
+    require(s_dev, "ucdir_fewstep_update_thresholded: null s_dev");
+    require((flags & ~(FEWSTEP_CLIP | FEWSTEP_FACTORED)) == 0, "fewstep update: unknown flags");
+    require(!(flags & FEWSTEP_CLIP), "ucdir_fewstep_update_thresholded: FEWSTEP_CLIP and a threshold exclude each other");
+    const FewstepCoef k{c_recip, c_recipm1, p, q, r, b1, sigma, flags, store_m != 0};
+    fewstep_launch("ucdir_fewstep_update_thresholded", x, eps, m_prev, noise, n, per, k, seed, seeds_dev, step, stream, s_dev, divide);
+    API_END
+}
+
+int64_t ucdir_fewstep_threshold_workspace_bytes(int64_t nsamples) {
+    if (nsamples < 0) return -1;
+    return (nsamples > 0 ? nsamples : 1) * (int64_t)(THR_WORDS * sizeof(uint32_t));
+}
+
+int32_t ucdir_fewstep_threshold(const float* x, const float* eps, int64_t n, int64_t per, float c_recip, float c_recipm1, double ratio,
+                                float max_val, float* s_dev, void* workspace, int64_t workspace_bytes, void* stream) {
+    API_BEGIN
+    const std::string w("ucdir_fewstep_threshold");
+    require(x && eps && s_dev && workspace, w + ": null argument");
+    require(n >= 0 && per > 0 && per % 4 == 0 && n % per == 0, w + ": n must be a whole number of samples of `per` elements, per a multiple of 4");
+    require(per < ((int64_t)1 << 31) && n / per <= 65535, w + ": at most 65535 samples of fewer than 2^31 elements");
+    require(ratio >= 0.0 && ratio <= 1.0, w + ": ratio must lie in [0, 1]");
+    require(max_val > 0.f, w + ": max_val must be positive");
+    const void* others[3] = {eps, s_dev, workspace};
+    const char* names[3] = {"eps", "s_dev", "workspace"};
+    const int device = same_device(w, x, "x", others, names, 3);
+    for (const void* q : {(const void*)x, (const void*)eps, (const void*)workspace})
+        require(((uintptr_t)q & 15) == 0, w + ": x, eps and the workspace must be 16-byte aligned");
+    require(((uintptr_t)s_dev & 3) == 0, w + ": s_dev must be 4-byte aligned");
+    const int64_t B = n / per, need = ucdir_fewstep_threshold_workspace_bytes(B);
+    require(workspace_bytes >= need, w + ": workspace too small (ucdir_fewstep_threshold_workspace_bytes)");
+    if (n == 0) return 0;
+    DevGuard dg(device);
+    hipStream_t st = (hipStream_t)stream;
+    // A = |x0| ascending: pos = ratio (per - 1), lo = floor(pos), hi = min(lo + 1, per - 1), w = pos - lo
+    const double pos = ratio * (double)(per - 1);
+    const uint32_t lo = (uint32_t)pos, hi = (int64_t)lo + 1 < per ? lo + 1 : lo;
+    const double frac = pos - (double)lo;
+    const long long per4 = per / 4;
+    long long wgs = (per4 + 255) / 256, cap = 1024 / B > 1 ? 1024 / B : 1;       // counts are integers: the split changes no result
+    if (wgs > cap) wgs = cap;
+    const dim3 grid((unsigned)wgs, (unsigned)B);
+    uint32_t* ws = (uint32_t*)workspace;
+    HIPC(hipMemsetAsync(workspace, 0, (size_t)need, st));
+    hipLaunchKernelGGL(threshold_hist_kernel<0>, grid, dim3(256), 0, st, x, eps, per4, c_recip, c_recipm1, ws);
+    hipLaunchKernelGGL(threshold_scan_kernel<0>, dim3((unsigned)B), dim3(256), 0, st, ws, lo, hi, frac, max_val, s_dev);
+    hipLaunchKernelGGL(threshold_hist_kernel<1>, grid, dim3(256), 0, st, x, eps, per4, c_recip, c_recipm1, ws);
+    hipLaunchKernelGGL(threshold_scan_kernel<1>, dim3((unsigned)B), dim3(256), 0, st, ws, lo, hi, frac, max_val, s_dev);
+    hipLaunchKernelGGL(threshold_hist_kernel<2>, grid, dim3(256), 0, st, x, eps, per4, c_recip, c_recipm1, ws);
+    hipLaunchKernelGGL(threshold_scan_kernel<2>, dim3((unsigned)B), dim3(256), 0, st, ws, lo, hi, frac, max_val, s_dev);
+    HIPC(hipGetLastError());
     API_END
 }
 

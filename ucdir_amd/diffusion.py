@@ -21,7 +21,9 @@ Differences from the reference, all result-preserving:
     the same sampler update to the gathered eps; SURVEY.md §8e);
   * ``sampler`` (``model.sampler`` in the YAML, ``sr.py --sampler``): when set, ``super_resolution`` restores with
     ``fewstep_sample`` - DDIM or DPM-Solver++ in 5-25 network calls instead of T, the update fused into one HIP kernel
-    (``ucdir_fewstep_update``) on the ancestral path's noise streams, buffers and graph replay.
+    (``ucdir_fewstep_update``) on the ancestral path's noise streams, buffers and graph replay.  DPM-Solver++ takes an optional
+    x0 ``thresholding`` (static, or Imagen's dynamic thresholding from an exact per-sample quantile kernel,
+    ``ucdir_fewstep_threshold``): without it the unclipped x0 runs away on this network.
 """
 from collections import namedtuple
 from functools import partial
@@ -31,7 +33,8 @@ import torch
 import torch.nn as nn
 
 from . import dpm_solver as D
-from .ucdir import FEWSTEP_CLIP, FEWSTEP_FACTORED, UNetSeeInDark, fewstep_update_, fill_normal_, sampler_step_, sampler_step_rng_
+from .ucdir import (FEWSTEP_CLIP, FEWSTEP_FACTORED, UNetSeeInDark, fewstep_threshold_, fewstep_threshold_workspace_bytes, fewstep_update_,
+                    fill_normal_, sampler_step_, sampler_step_rng_)
 
 SAMPLERS = ("ddpm", "ddim", "dpm_solver++")
 TIME_INPUTS = ("level", "reference")
@@ -43,7 +46,8 @@ FewStep = namedtuple("FewStep", "level c_recip c_recipm1 flags p q r b1 store_m 
 def parse_sampler(spec):
     """``model.sampler`` of the YAML -> None (the T-step ancestral sampler) or a complete dict of ``fewstep_sample`` arguments.
     Absent, empty or ``name: ddpm`` keeps today's path.  Defaults: DDIM 5 steps (the reference's ddim_sampling), DPM-Solver++ 20
-    steps (its dpm_solver driver), order 2, eta 1, the network fed the noise level it is trained on."""
+    steps (its dpm_solver driver), order 2, eta 1, the network fed the noise level it is trained on.  ``thresholding`` (a kind, or a
+    mapping with kind / max_val / ratio; DPM-Solver++ only) is returned only when it is on."""
     if not spec or spec.get("name") == "ddpm":
         return None
     if not spec.get("name"):
@@ -57,6 +61,11 @@ def parse_sampler(spec):
            "eta": float(get("eta", 1.0)), "time_input": get("time_input", "level")}
     if out["steps"] < 1 or out["order"] not in (1, 2) or out["eta"] < 0 or out["time_input"] not in TIME_INPUTS:
         raise ValueError("bad model.sampler %r: steps >= 1, order 1 or 2, eta >= 0, time_input one of %s" % (dict(spec), TIME_INPUTS))
+    thresholding = D.parse_thresholding(spec.get("thresholding"))
+    if thresholding is not None:
+        if name != "dpm_solver++":
+            raise ValueError("model.sampler.thresholding is DPM-Solver++'s x0 correction: %s keeps its clamp of x0 to [-1, 1]" % name)
+        out["thresholding"] = thresholding
     return out
 
 
@@ -319,10 +328,11 @@ class GaussianDiffusion(nn.Module):
         return img
 
     @torch.no_grad()
-    def dpm_solver_sample(self, x_in, steps=20, order=2, kwargs={}):
+    def dpm_solver_sample(self, x_in, steps=20, order=2, kwargs={}, thresholding=None):
         """The sampler of the reference's ``dpm_solver()`` driver (sr.py:185-231): DPM-Solver++ multistep on the discrete
         schedule ``self.betas``, the network conditioned on ``x_in`` (channel concat) and on ``guide``; the caller adds
-        ``initx``.  ``steps`` UNet forwards instead of ``num_timesteps``."""
+        ``initx``.  ``steps`` UNet forwards instead of ``num_timesteps``.  ``thresholding``: the x0 correction in torch ops
+        (``dpm_solver.correct_x0``)."""
         from . import dpm_solver as D
         ns = D.NoiseScheduleVP(self.betas)
         guide = kwargs.get("guide")
@@ -335,11 +345,11 @@ class GaussianDiffusion(nn.Module):
         self._begin()
         try:
             self._start_noise(x_in.device)
-            return D.sample(model_eps, ns, self._noise(x_in, 0), steps=steps, order=order)
+            return D.sample(model_eps, ns, self._noise(x_in, 0), steps=steps, order=order, thresholding=thresholding)
         finally:
             self._end()
 
-    def fewstep_plan(self, sampler, steps, order=2, eta=1.0, time_input="level"):
+    def fewstep_plan(self, sampler, steps, order=2, eta=1.0, time_input="level", thresholding=None):
         """The per-call table of ``fewstep_sample`` (host, float64): one ``FewStep`` per network call.
 
         * ``ddim``: the pairs of ``_ddim_steps`` (``linspace(-1, T-1, steps+1).int()``), its level, c_recip / c_recipm1 and its
@@ -348,7 +358,11 @@ class GaussianDiffusion(nn.Module):
           step below 10 steps); x0 = (x - sigma_s eps) / alpha_s (the kernel's factored form), x <- a x + b0 x0 + b1 x0_prev
           (``dpm_solver.multistep_coefficients``).
           The network sees the noise level sqrt(abar(s)) = alpha_s (``time_input="level"``: what DY3h is conditioned on, as in every
-          other sampler here) or the reference driver's time index (s - 1/N) * 1000 (``"reference"``, sr.py:141-147)."""
+          other sampler here) or the reference driver's time index (s - 1/N) * 1000 (``"reference"``, sr.py:141-147).
+
+        ``thresholding`` (DPM-Solver++ only) changes no coefficient: the correction acts on x0 inside the update."""
+        if D.parse_thresholding(thresholding) is not None and sampler == "ddim":
+            raise ValueError("thresholding is DPM-Solver++'s x0 correction: ddim keeps its clamp of x0 to [-1, 1] (clip_x_start)")
         if sampler == "ddim":
             T = self.num_timesteps
             times = list(reversed(torch.linspace(-1, T - 1, steps=steps + 1).int().tolist()))
@@ -389,29 +403,40 @@ class GaussianDiffusion(nn.Module):
         raise ValueError("fewstep_sample: sampler must be 'ddim' or 'dpm_solver++', got %r" % (sampler,))
 
     @torch.no_grad()
-    def fewstep_sample(self, x_in, sampler, steps, order=2, eta=1.0, time_input="level", continous=False, kwargs={}):
+    def fewstep_sample(self, x_in, sampler, steps, order=2, eta=1.0, time_input="level", continous=False, kwargs={}, thresholding=None):
         """DDIM (model/diffusion.py:247-294) or DPM-Solver++ 2M (the reference's dpm_solver driver, sr.py:185-231) in ``steps``
         network calls, each followed by ONE fused update launch (``ucdir_fewstep_update``).  Same plumbing as ``p_sample_loop``:
         x_T and DDIM's per-step noise come from the in-kernel Philox streams (``sample_seeds`` / ``noise_seed`` honoured, DDIM
         noise counter k = 1, 2, ...) or from ``noise_source``; cond / x_t / eps / level live in the persistent buffers graph
         replay needs, plus one x0-history buffer for DPM-Solver++; images above ``patch_threshold`` take the patch split.
-        ``continous``: dim-0 blocks of B - the input, then x after every call (the final result last), as p_sample_loop."""
+        ``continous``: dim-0 blocks of B - the input, then x after every call (the final result last), as p_sample_loop.
+        ``thresholding`` (``dpm_solver++`` only; ``{"kind": "static" | "dynamic", "max_val": 1.0, "ratio": 0.995}``): x0 is
+        corrected inside the update launch (``ucdir_fewstep_update_thresholded``); ``dynamic`` first selects every sample's
+        threshold over its C H W elements (``ucdir_fewstep_threshold``) - on images above ``patch_threshold`` that is the whole
+        canvas, whatever the window split.  None: today's arithmetic."""
         if not self.conditional:
             raise NotImplementedError("unconditional sampling is not part of the UCDIR restoration path")
-        plan = self.fewstep_plan(sampler, steps, order, eta, time_input)
+        plan = self.fewstep_plan(sampler, steps, order, eta, time_input, thresholding)
         x = x_in.contiguous().float()
         self._begin()
         try:
-            ret = self._fewstep_steps(x, kwargs.get("guide"), plan, continous)
+            ret = self._fewstep_steps(x, kwargs.get("guide"), plan, continous, D.parse_thresholding(thresholding))
         finally:
             self._end()
         return torch.cat(ret, dim=0) if continous else ret[-1]
 
-    def _fewstep_steps(self, x, guide, plan, continous):
+    def _fewstep_steps(self, x, guide, plan, continous, thresholding=None):
         self._start_noise(x.device, kernel_rng=True)
         seeds = self._seeds_tensor(x)
         cond, img, eps_buf, lvl = self._loop_buffers(x, seeds)
         m_prev = torch.empty_like(x) if any(s.store_m for s in plan) else None
+        B, per = x.shape[0], x.numel() // x.shape[0]
+        thr = ws = None                                             # per-sample thresholds and the selection's workspace: once per restoration
+        dynamic = thresholding is not None and thresholding["kind"] == "dynamic"
+        if thresholding is not None:
+            thr = torch.full((B,), thresholding["max_val"], dtype=torch.float32, device=x.device)
+        if dynamic:
+            ws = torch.empty(fewstep_threshold_workspace_bytes(B), dtype=torch.uint8, device=x.device)
         injected = self.noise_source is not None
         seed = 0 if injected else self._kseed
         ret = [x]
@@ -419,8 +444,10 @@ class GaussianDiffusion(nn.Module):
             lvl.fill_(s.level)
             eps = self._eps(cond, img, lvl, guide, out=eps_buf)
             noise = self._noise(img, s.k) if injected and s.sigma != 0.0 else None
+            if dynamic:
+                fewstep_threshold_(img, eps, per, s.c_recip, s.c_recipm1, thresholding["ratio"], thresholding["max_val"], out=thr, workspace=ws)
             fewstep_update_(img, eps, m_prev, s.c_recip, s.c_recipm1, s.flags, s.p, s.q, s.r, s.b1, s.store_m, s.sigma,
-                            seed=seed, step=s.k, seeds=seeds, noise=noise)
+                            seed=seed, step=s.k, seeds=seeds, noise=noise, s=thr, divide=dynamic)
             if continous:
                 ret.append(img.clone())
         return ret if continous else [img.clone()]                  # (img may be the persistent graph-replay buffer)

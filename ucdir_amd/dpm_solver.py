@@ -4,8 +4,15 @@ reference, no version pinned).  That package is absent here, so this is a restat
 (Lu et al., "DPM-Solver++", 2022: data-prediction multistep solver, discrete-time VP schedule), limited to what
 the reference's call uses: ``NoiseScheduleVP('discrete', betas)``, ``algorithm_type='dpmsolver++'``,
 ``sample(steps, order=2, skip_type='time_uniform', method='multistep')``, ``lower_order_final`` only below
-10 steps, no thresholding, no denoise-to-zero.  **Parity unpinned** against the package itself (DESIGN.md §2);
+10 steps, no denoise-to-zero.  **Parity unpinned** against the package itself (DESIGN.md §2);
 ``tests`` pin it against an independent oracle restatement and against closed forms of the schedule.
+
+x0 thresholding (``thresholding=``, off by default as in the reference's call): the package's ``correcting_x0_fn``.
+``dynamic`` is its ``"dynamic_thresholding"`` (Imagen): per sample s = max(quantile(|x0|, ratio), max_val), x0 clamped
+to +-s and divided by s; ``static`` clamps to +-max_val.  The quantile is taken from a sort and interpolated in float64
+(``dynamic_threshold``) - the rule the HIP selection kernel implements exactly (csrc/fewstep.hip.h), where the package
+calls ``torch.quantile`` in the working precision.  The corrected x0 is also the solver's history.  What either does to
+restoration quality on trained weights is unmeasured.
 
 All schedule arithmetic is host-side float64; the per-step tensor update is three fused multiply-adds over
 B x 3 x H x W (HBM-trivial, plain torch ops); the cost is the UNet forward, which runs on the HIP engine.
@@ -66,17 +73,68 @@ def multistep_coefficients(ns: NoiseScheduleVP, t_prev_list, t: float, order: in
     return a, -alpha_t * phi1 + c, -c
 
 
+THRESHOLDING_KINDS = ("static", "dynamic")
+
+
+def parse_thresholding(value):
+    """A thresholding setting -> None (off) or the complete dict ``{"kind", "max_val", "ratio"}``.  ``value``: None / "none", a kind
+    ("static", "dynamic") or a mapping with ``kind`` and optionally ``max_val`` (default 1.0) and ``ratio`` (0.995, the package's)."""
+    if value is None or value == "none":
+        return None
+    spec = {"kind": value} if isinstance(value, str) else dict(value)
+    kind = spec.get("kind")
+    if kind is None or kind == "none":
+        return None
+    unknown = set(spec) - {"kind", "max_val", "ratio"}
+    if kind not in THRESHOLDING_KINDS or unknown:
+        raise ValueError("thresholding must be none, %s or a mapping with kind, max_val, ratio; got %r" % (", ".join(THRESHOLDING_KINDS), value))
+    max_val = 1.0 if spec.get("max_val") is None else float(spec["max_val"])
+    ratio = 0.995 if spec.get("ratio") is None else float(spec["ratio"])
+    if not max_val > 0.0 or not 0.0 < ratio <= 1.0:
+        raise ValueError("thresholding needs max_val > 0 and ratio in (0, 1]; got %r" % (value,))
+    return {"kind": kind, "max_val": max_val, "ratio": ratio}
+
+
+def dynamic_threshold(x0, ratio, max_val):
+    """s of every sample of ``x0`` (B, ...), shape (B,): with A = the sample's |x0| in ascending order (NaN last),
+    pos = ratio (per - 1), lo = floor(pos), hi = min(lo + 1, per - 1), w = pos - lo, the quantile is A[lo] when A[lo] == A[hi] and
+    A[lo] + w (A[hi] - A[lo]) in float64 otherwise, rounded once to x0's precision; NaN when the sample holds one;
+    s = max(quantile, max_val)."""
+    a = x0.abs().reshape(x0.shape[0], -1)
+    per = a.shape[1]
+    A = torch.sort(a, dim=1).values
+    pos = float(ratio) * (per - 1)
+    lo = int(math.floor(pos))
+    hi = min(lo + 1, per - 1)
+    alo, ahi = A[:, lo].double(), A[:, hi].double()
+    q = torch.where(alo == ahi, alo, alo + (pos - lo) * (ahi - alo)).to(x0.dtype)
+    q = torch.where(torch.isnan(a).any(dim=1), torch.full_like(q, float("nan")), q)
+    return q.clamp(min=float(max_val))                                  # (a NaN quantile stays NaN)
+
+
+def correct_x0(x0, thresholding):
+    """The x0 correction of ``parse_thresholding``'s dict on ``x0`` (B, ...), in torch ops; None returns ``x0`` itself."""
+    if thresholding is None:
+        return x0
+    if thresholding["kind"] == "static":
+        return x0.clamp(-thresholding["max_val"], thresholding["max_val"])
+    s = dynamic_threshold(x0, thresholding["ratio"], thresholding["max_val"]).view((-1,) + (1,) * (x0.dim() - 1))
+    return torch.clamp(x0, -s, s) / s
+
+
 @torch.no_grad()
-def sample(model_eps, ns: NoiseScheduleVP, x_T: torch.Tensor, steps: int = 20, order: int = 2):
+def sample(model_eps, ns: NoiseScheduleVP, x_T: torch.Tensor, steps: int = 20, order: int = 2, thresholding=None):
     """``DPM_Solver(model_fn, ns, algorithm_type='dpmsolver++').sample(x_T, steps, order, 'time_uniform', 'multistep')``.
 
-    ``model_eps(x, t)`` returns the noise prediction at continuous time t in [1/N, 1]."""
+    ``model_eps(x, t)`` returns the noise prediction at continuous time t in [1/N, 1].  ``thresholding``: the x0 correction
+    (``parse_thresholding``), applied inside the data prediction - the history holds corrected predictions."""
     assert order in (1, 2) and steps >= order
+    thresholding = parse_thresholding(thresholding)
     t_T, t_0 = ns.T, 1.0 / ns.total_N
     ts = [float(v) for v in np.linspace(t_T, t_0, steps + 1)]
 
     def data_pred(x, t):
-        return (x - ns.marginal_std(t) * model_eps(x, t)) / ns.marginal_alpha(t)
+        return correct_x0((x - ns.marginal_std(t) * model_eps(x, t)) / ns.marginal_alpha(t), thresholding)
 
     x = x_T
     t_prev, m_prev = [ts[0]], [data_pred(x, ts[0])]

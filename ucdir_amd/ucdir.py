@@ -396,11 +396,14 @@ def sampler_step_rng_(x_t, eps, seed, step, c_recip, c_recipm1, coef1, coef2, si
 FEWSTEP_CLIP, FEWSTEP_FACTORED = 1, 2      # flags of fewstep_update_
 
 
-def fewstep_update_(x, eps, m_prev, c_recip, c_recipm1, flags, p, q, r, b1, store_m, sigma, seed=0, step=0, seeds=None, noise=None):
+def fewstep_update_(x, eps, m_prev, c_recip, c_recipm1, flags, p, q, r, b1, store_m, sigma, seed=0, step=0, seeds=None, noise=None,
+                    s=None, divide=False):
     """In-place update of the few-step samplers (csrc/fewstep.hip.h):
     x0 = c_recip x - c_recipm1 eps (``FEWSTEP_FACTORED``: c_recip (x - c_recipm1 eps); ``FEWSTEP_CLIP``: clamped to [-1, 1]),
     x <- p x0 + q x + r eps + b1 m_prev + sigma z, m_prev <- x0 when ``store_m``.  z is the noise of (seed, step, element) drawn in the kernel (``seeds``: per-sample streams as in ``sampler_step_rng_``),
-    or ``noise`` when given.  ``m_prev`` may be None when b1 == 0 and not ``store_m``."""
+    or ``noise`` when given.  ``m_prev`` may be None when b1 == 0 and not ``store_m``.
+    ``s`` (fp32 CUDA tensor, one threshold per sample of x): x0 is clamped to +-s[b], and divided by s[b] when ``divide``, before it
+    is used and stored (``ucdir_fewstep_update_thresholded``; ``fewstep_threshold_`` computes the dynamic s)."""
     L = _lib.load()
 
     def ok(t):
@@ -415,12 +418,60 @@ def fewstep_update_(x, eps, m_prev, c_recip, c_recipm1, flags, p, q, r, b1, stor
     nz = _ptr(noise) if noise is not None else ctypes.c_void_p(0)
     if seeds is not None:
         _check_seeds(seeds, x, "fewstep_update_")
+    if s is not None:
+        _check_per_sample(s, x, "fewstep_update_: s")
+        _lib.check(L.ucdir_fewstep_update_thresholded(_ptr(x), _ptr(eps), mp, nz, x.numel(), x.numel() // x.shape[0], *coef,
+                                                      int(seed) & (2 ** 64 - 1), _ptr(seeds) if seeds is not None else ctypes.c_void_p(0),
+                                                      int(step), _ptr(s), int(bool(divide)), _stream_ptr(x.device)))
+        return x
+    if seeds is not None:
         _lib.check(L.ucdir_fewstep_update_batched(_ptr(x), _ptr(eps), mp, nz, x.numel(), x.numel() // x.shape[0], *coef, _ptr(seeds),
                                                   int(step), _stream_ptr(x.device)))
         return x
     _lib.check(L.ucdir_fewstep_update(_ptr(x), _ptr(eps), mp, nz, x.numel(), *coef, int(seed) & (2 ** 64 - 1), int(step),
                                       _stream_ptr(x.device)))
     return x
+
+
+def _check_per_sample(t, x, who):
+    """A per-sample fp32 vector of ``x``: one entry per sample, on its device (samples of a multiple of 4 elements)."""
+    if not (torch.is_tensor(t) and t.is_cuda and t.device == x.device and t.dtype == torch.float32 and t.is_contiguous()
+            and x.dim() >= 2 and t.numel() == x.shape[0] and (x.numel() // x.shape[0]) % 4 == 0):
+        raise _lib.UcdirError(who + " must be a contiguous fp32 CUDA tensor with one entry per sample of x "
+                                    "(samples of a multiple of 4 elements)")
+
+
+def fewstep_threshold_workspace_bytes(nsamples):
+    """Bytes of workspace ``fewstep_threshold_`` needs for ``nsamples`` samples (a host query)."""
+    return int(_lib.load().ucdir_fewstep_threshold_workspace_bytes(int(nsamples)))
+
+
+def fewstep_threshold_(x, eps, per, c_recip, c_recipm1, ratio, max_val, out=None, workspace=None):
+    """Dynamic x0 threshold of every sample (csrc/fewstep.hip.h, ``ucdir_fewstep_threshold``): x and eps hold numel / ``per``
+    samples of ``per`` elements; returns s (fp32, one per sample) with s[b] = max(quantile(|x0_b|, ratio), max_val) for
+    x0 = c_recip (x - c_recipm1 eps), the quantile selected exactly (linear interpolation between the two order statistics in
+    float64; NaN when the sample holds one).  ``out`` and ``workspace`` (uint8, ``fewstep_threshold_workspace_bytes``) are
+    allocated when not given; a sampling loop passes both, and the call then neither allocates nor synchronises."""
+    L = _lib.load()
+    if not (x.is_cuda and x.is_contiguous() and x.dtype == torch.float32):
+        raise _lib.UcdirError("fewstep_threshold_ needs a contiguous fp32 CUDA tensor")
+    if not (eps.is_cuda and eps.is_contiguous() and eps.dtype == torch.float32 and eps.numel() == x.numel() and eps.device == x.device):
+        raise _lib.UcdirError("fewstep_threshold_: eps must be a contiguous fp32 CUDA tensor shaped like x on its device")
+    per = int(per)
+    if per <= 0 or per % 4 or x.numel() % per:
+        raise _lib.UcdirError("fewstep_threshold_: x must hold a whole number of samples of `per` elements, per a multiple of 4")
+    B = x.numel() // per
+    if out is None:
+        out = torch.empty(B, dtype=torch.float32, device=x.device)
+    elif not (out.is_cuda and out.device == x.device and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == B):
+        raise _lib.UcdirError("fewstep_threshold_: out must be a contiguous fp32 CUDA tensor with one entry per sample, on the device of x")
+    if workspace is None:
+        workspace = torch.empty(fewstep_threshold_workspace_bytes(B), dtype=torch.uint8, device=x.device)
+    elif not (workspace.is_cuda and workspace.device == x.device and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
+        raise _lib.UcdirError("fewstep_threshold_: workspace must be a contiguous uint8 CUDA tensor on the device of x")
+    _lib.check(L.ucdir_fewstep_threshold(_ptr(x), _ptr(eps), x.numel(), per, float(c_recip), float(c_recipm1), float(ratio),
+                                         float(max_val), _ptr(out), _ptr(workspace), workspace.numel(), _stream_ptr(x.device)))
+    return out
 
 
 def gather_windows(x, pad, win_dev, skip):
