@@ -193,6 +193,42 @@ int32_t ucdir_fewstep_update_thresholded(float* x, const float* eps, float* m_pr
 int64_t ucdir_fewstep_threshold_workspace_bytes(int64_t nsamples);
 int32_t ucdir_fewstep_threshold(const float* x, const float* eps, int64_t n, int64_t per, float c_recip, float c_recipm1,
                                 double ratio, float max_val, float* s_dev, void* workspace, int64_t workspace_bytes, void* stream);
+/* The forward half of the denoising loss (model/diffusion.py:306-343, 444-471; additive in ABI 5): B samples of `per` fp32 elements.
+ *
+ * ucdir_qsample noises the diffused image at one level per sample, read on the device (no host synchronisation):
+ *   x_start = hr - x_init                           (x_init == NULL: hr)
+ *   x_noisy = level[b] * x_start + sqrt(1 - level[b] * level[b]) * z
+ * every difference, product, square root and sum rounded to fp32 on its own (no FMA contraction, sqrt correctly rounded), as the
+ * reference's chain of torch ops rounds them.  level[b] == 1 gives x_start exactly; a level outside [0, 1] gives what the
+ * reference gives (NaN above 1).  z is `noise` (B * per elements) when non-NULL; otherwise the standard normal ucdir_fill_normal
+ * draws for (seed, step, flat element) when seeds_dev == NULL, or ucdir_fill_normal_batched draws for (seeds_dev[b], step, element
+ * of the sample).  Without seeds any per >= 1 is allowed: a group of four elements may then straddle two samples, and each element
+ * takes its own sample's level.  With seeds per must be a multiple of 4.
+ *   read:    hr, level (B floats), and when non-NULL x_init, noise, seeds_dev (B uint64)
+ *   written: every element of x_noisy and, when non-NULL, of z_out (the z used); nothing else
+ *   NULL allowed: x_init, z_out, noise, seeds_dev.  hr, x_init, x_noisy, z_out, noise: 16-byte aligned; level 4, seeds_dev 8.
+ *   x_noisy may not alias an input.  All pointers on one device.
+ *
+ * ucdir_noise_loss reduces the noise-prediction error per sample, from one pass over eps:
+ *   l1[b] = sum_i |z_i - eps_i|,   l2[b] = sum_i fl32((z_i - eps_i)^2)
+ * fp32 terms (difference and square each rounded to fp32) summed in float64.  z as above: `noise`, or regenerated from
+ * (seed | seeds_dev[b], step, element) so that no noise tensor has to outlive the forward.  Stage one writes one partial pair per
+ * (sample, block of 4096 elements) through a fixed xor / LDS tree, stage two adds a sample's partials lane-strided in a fixed
+ * order; no floating-point atomics.  The shape of every sum depends on `per` alone - not on B or the launch - so a sample's
+ * (l1, l2) has the same bits alone, in any batch and from run to run.
+ *   read:    eps (B * per floats), and when non-NULL noise, seeds_dev
+ *   written: l1[0..B), l2[0..B) (doubles) and the first ucdir_noise_loss_workspace_bytes(B, per) bytes of the workspace, whose
+ *            contents before the call are arbitrary and never read unwritten
+ *   NULL allowed: noise, seeds_dev.  eps, noise, workspace: 16-byte aligned; l1, l2, seeds_dev 8.
+ * ucdir_noise_loss_workspace_bytes is a host query: B * ceil(per / 4096) * 16 bytes, at least 16; -1 for B < 0, per < 1 or overflow.
+ *
+ * In both calls every argument check (NULL, B < 0, per < 1, per % 4 != 0 with seeds, alignment, workspace size) precedes the first
+ * device call, and B == 0 returns before it.  Neither synchronises or allocates: both can be captured in a graph. */
+int32_t ucdir_qsample(const float* hr, const float* x_init, const float* level, float* x_noisy, float* z_out, const float* noise,
+                      int64_t B, int64_t per, uint64_t seed, const uint64_t* seeds_dev, uint32_t step, void* stream);
+int64_t ucdir_noise_loss_workspace_bytes(int64_t B, int64_t per);
+int32_t ucdir_noise_loss(const float* eps, const float* noise, int64_t B, int64_t per, uint64_t seed, const uint64_t* seeds_dev,
+                         uint32_t step, double* l1, double* l2, void* workspace, int64_t workspace_bytes, void* stream);
 /* Window batch of the inter-step patch split (utils/util.py:113-137: F.pad(..., mode='reflect') then one slice per window) in ONE launch,
  * straight from the un-padded canvas: out[(w * B + b)][c][y][x] = x[b][c][refl(h0_w + y - pad)][refl(w0_w + x - pad)], x (B, C, H, W) fp32,
  * out (nwin * B, C, skip, skip) fp32, win_dev = nwin pairs (h0, w0) of int32 ON THE DEVICE in padded coordinates (the window list of

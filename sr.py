@@ -85,6 +85,34 @@ def image_seed_base(seed):
     return base
 
 
+def parse_val_loss_steps(text, T):
+    """``--val-loss-t 1,50,...`` -> the list of steps, each in [1, T]; None when the flag is absent."""
+    if text is None:
+        return None
+    try:
+        ts = [int(v) for v in text.split(",") if v.strip()]
+    except ValueError:
+        raise SystemExit("--val-loss-t wants comma-separated integers, got %r" % text)
+    if not ts or any(not 1 <= t <= T for t in ts):
+        raise SystemExit("--val-loss-t: every step must lie in [1, %d], got %r" % (T, text))
+    return ts
+
+
+def val_loss_table(opt, which):
+    """The noise levels the loss is evaluated on (``--val-loss-schedule``): sqrt of the cumulative alpha product of
+    ``model.beta_schedule[which]`` with a leading 1 - the trainer's ``sqrt_alphas_cumprod_prev`` for ``train`` - built here, so the
+    sampler's buffers (set for the val schedule) are not touched."""
+    from ucdir_amd.diffusion import make_beta_schedule
+    so = opt["model"]["beta_schedule"][which]
+    betas = make_beta_schedule(schedule=so["schedule"], n_timestep=so["n_timestep"], linear_start=so["linear_start"], linear_end=so["linear_end"])
+    return np.sqrt(np.append(1.0, np.cumprod(1.0 - betas, axis=0)))
+
+
+def val_index_line(i, l_pix=None):
+    """The per-image val log line; ``l_pix`` is appended only under ``--val-loss``."""
+    return "val index %d" % i if l_pix is None else "val index %d l_pix: %.4e" % (i, l_pix)
+
+
 def make_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument("-c", "--config", type=str, default="config/sid.yaml")
@@ -132,11 +160,21 @@ def make_parser():
                              "reference's eval1.py")
     parser.add_argument("--lpips-weights", type=str, nargs="+", default=[], metavar="FILE",
                         help="LPIPS weights: torchvision's AlexNet state dict and the lpips package's alex.pth (.pth or .npz), merged")
+    parser.add_argument("--val-loss", type=int, default=0, metavar="K",
+                        help="also evaluate the denoising loss l_pix of every val image: K random (step, level) draws per image, seeded "
+                             "per image index (0: off)")
+    parser.add_argument("--val-loss-t", type=str, default=None, metavar="T1,T2,...",
+                        help="with --val-loss: evaluate at these steps (K level draws each) instead of random ones, and print a per-step table")
+    parser.add_argument("--val-loss-schedule", choices=["train", "val"], default="train",
+                        help="beta schedule whose noise levels --val-loss draws from (default: train, the one the loss is defined on)")
     return parser
 
 
 def main(argv=None):
-    args = make_parser().parse_args(argv)
+    parser = make_parser()
+    args = parser.parse_args(argv)
+    if args.val_loss_t is not None and args.val_loss <= 0:
+        parser.error("--val-loss-t needs --val-loss K (K >= 1 level draws per step)")
     if args.phase != "val":
         raise SystemExit("only -p val is implemented (sampling path); training is out of scope of this build")
     # a missing LPIPS weight file or tensor stops the run here, before a device is touched or the model is built
@@ -175,8 +213,13 @@ def main(argv=None):
     logger.info("Begin Model Evaluation. len %d" % len(val_set))
     result_path = opt["path"]["results"]
     os.makedirs(result_path, exist_ok=True)
-    tot_psnr = tot_ssim = tot_niqe = tot_lpips = 0.0
+    tot_psnr = tot_ssim = tot_niqe = tot_lpips = tot_lpix = 0.0
     n = 0
+    loss_table = loss_ts = None
+    loss_steps = {}                                               # step -> [sum of l_pix, images] under --val-loss-t
+    if args.val_loss > 0:
+        loss_table = val_loss_table(opt, args.val_loss_schedule)
+        loss_ts = parse_val_loss_steps(args.val_loss_t, len(loss_table) - 1)
     idxs = list(range(len(val_set)))
     if args.max_images > 0:
         idxs = idxs[:args.max_images * world]
@@ -192,7 +235,7 @@ def main(argv=None):
     def restore(group):
         """One DDPM.test call for a group of images of identical (H, W): a batch is B independent restorations (model/diffusion.py:185-211
         is written for a batch; the reference's val loader feeds it batch_size 1, data/__init__.py:47)."""
-        nonlocal tot_psnr, tot_ssim, tot_niqe, tot_lpips, n, t_restore, n_restored
+        nonlocal tot_psnr, tot_ssim, tot_niqe, tot_lpips, tot_lpix, n, t_restore, n_restored
         items = [g[1] for g in group]
         data = {k: torch.stack([it[k] for it in items]) for k in ("HR", "SR", "LR", "gt", "lq") if k in items[0]}
         data["Index"] = [g[0] for g in group]                    # DDPM.test derives every image's noise stream from its index
@@ -208,8 +251,21 @@ def main(argv=None):
         t_restore += time.perf_counter() - t0
         n_restored += len(group)
         group_times.append((len(group), time.perf_counter() - t0))
+        l_pix = None
+        if loss_table is not None:                                # outside the timed restoration; every rank of a sharded image takes part
+            # the loss's forwards run on fresh tensors: without replay they leave no graphs behind.  Switching replay off drops the
+            # restoration's graph, so under --val-loss a batch-1 restoration captures its forward again for every image.
+            replay = dn.use_graph
+            dn.set_graph(False)
+            l_pix, per_step = diffusion.val_loss(args.val_loss, loss_ts, loss_table, seed=args.seed or 0)
+            dn.set_graph(replay)
         if group[0][2] and rank != 0:
             return                                                # sharded image: every rank holds the same result; rank 0 reports it
+        if l_pix is not None:                                     # counted once: by rank 0 for a sharded image, by its rank otherwise
+            for t, vals in per_step.items():
+                acc_t = loss_steps.setdefault(t, [0.0, 0])
+                acc_t[0] += sum(vals)
+                acc_t[1] += len(vals)
         name = opt["name"]
         dev_scores = diffusion.current_metrics() if args.metrics_device == "gpu" else None
         dev_niqe = diffusion.current_niqe() if args.niqe and args.metrics_device == "gpu" else None
@@ -241,7 +297,9 @@ def main(argv=None):
             if args.lpips:
                 tot_lpips += dev_lpips[j] if dev_lpips is not None else Metrics.calculate_lpips(sr_img, hr_img, lpips_weights)
             n += 1
-            logger.info("val index %d" % i)
+            if l_pix is not None:
+                tot_lpix += l_pix[j]
+            logger.info(val_index_line(i, None if l_pix is None else l_pix[j]))
 
     pending = {}                                                  # (H, W) -> images of this rank waiting for a full batch (first-seen order)
     nsmall = 0
@@ -277,7 +335,7 @@ def main(argv=None):
         logger.info("decoded on the GPU; %d images fell back to Pillow%s" % (
             len(main.last_decode_fallbacks), "".join(" [%d: %s]" % f for f in main.last_decode_fallbacks[:8])))
     main.last_groups = group_times
-    acc = torch.tensor([tot_psnr, tot_ssim, float(n), tot_niqe, tot_lpips], dtype=torch.float64, device="cuda")
+    acc = torch.tensor([tot_psnr, tot_ssim, float(n), tot_niqe, tot_lpips, tot_lpix], dtype=torch.float64, device="cuda")
     if world > 1:
         dist.all_reduce(acc)
     avg_psnr, avg_ssim = (acc[0] / acc[2]).item(), (acc[1] / acc[2]).item()
@@ -292,6 +350,16 @@ def main(argv=None):
     if args.lpips:
         logger.info("# Validation # LPIPS: {:.4e}".format(main.last_lpips))
         line += ", lpips: {:.4e}".format(main.last_lpips)
+    main.last_l_pix = (acc[5] / acc[2]).item() if loss_table is not None else None
+    if loss_table is not None:
+        logger.info("# Validation # l_pix: {:.4e}".format(main.last_l_pix))
+        line += ", l_pix: {:.4e}".format(main.last_l_pix)
+        steps = torch.tensor([loss_steps.get(t, [0.0, 0]) for t in (loss_ts or [])], dtype=torch.float64, device="cuda").reshape(-1, 2)
+        if world > 1 and steps.numel():
+            dist.all_reduce(steps)                                # every rank holds the same --val-loss-t: one row per step
+        for t, (tot, cnt) in zip(loss_ts or [], steps.tolist()):
+            if cnt:
+                logger.info("# Validation # l_pix at step %d: %.4e (%d images)" % (t, tot / cnt, int(cnt)))
     logging.getLogger("val").info(line)
     if world > 1:
         dist.destroy_process_group()

@@ -4,6 +4,7 @@
 #include "api_common.h"
 #include "sampler.hip.h"
 #include "fewstep.hip.h"
+#include "loss.hip.h"
 
 extern "C" {
 
@@ -177,6 +178,68 @@ int32_t ucdir_fewstep_threshold(const float* x, const float* eps, int64_t n, int
     hipLaunchKernelGGL(threshold_scan_kernel<1>, dim3((unsigned)B), dim3(256), 0, st, ws, lo, hi, frac, max_val, s_dev);
     hipLaunchKernelGGL(threshold_hist_kernel<2>, grid, dim3(256), 0, st, x, eps, per4, c_recip, c_recipm1, ws);
     hipLaunchKernelGGL(threshold_scan_kernel<2>, dim3((unsigned)B), dim3(256), 0, st, ws, lo, hi, frac, max_val, s_dev);
+    HIPC(hipGetLastError());
+    API_END
+}
+
+// ---- the denoising loss's forward half (csrc/loss.hip.h) --------------------------------------------------------------------------------
+// the shape checks ucdir_qsample and ucdir_noise_loss share; every one precedes the first device call
+static void loss_shape(const std::string& w, int64_t B, int64_t per, const void* seeds_dev) {
+    require(B >= 0, w + ": negative sample count");
+    require(per >= 1, w + ": per must be at least 1");
+    require(B == 0 || per <= INT64_MAX / 4 / B, w + ": B * per overflows");
+    require(!seeds_dev || per % 4 == 0, w + ": per-sample seeds need samples of a multiple of 4 elements");
+}
+
+int32_t ucdir_qsample(const float* hr, const float* x_init, const float* level, float* x_noisy, float* z_out, const float* noise,
+                      int64_t B, int64_t per, uint64_t seed, const uint64_t* seeds_dev, uint32_t step, void* stream) {
+    API_BEGIN
+    const std::string w("ucdir_qsample");
+    require(hr && level && x_noisy, w + ": null argument (hr, level and x_noisy are needed)");
+    loss_shape(w, B, per, seeds_dev);
+    for (const void* q : {(const void*)hr, (const void*)x_init, (const void*)x_noisy, (const void*)z_out, (const void*)noise})
+        require(((uintptr_t)q & 15) == 0, w + ": hr, x_init, x_noisy, z_out and noise must be 16-byte aligned");
+    require(((uintptr_t)level & 3) == 0 && ((uintptr_t)seeds_dev & 7) == 0, w + ": level must be 4-byte and seeds 8-byte aligned");
+    if (B == 0) return 0;
+    const void* others[6] = {hr, x_init, level, z_out, noise, seeds_dev};
+    const char* names[6] = {"hr", "x_init", "level", "z_out", "noise", "seeds"};
+    DevGuard dg(same_device(w, x_noisy, "x_noisy", others, names, 6));
+    const long long n = B * per;
+    long long blocks = ((n + 3) / 4 + 255) / 256; if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(qsample_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, hr, x_init, level, x_noisy, z_out, noise, n,
+                       (long long)per, (unsigned long long)seed, step, (const unsigned long long*)seeds_dev, (long long)(per / 4));
+    HIPC(hipGetLastError());
+    API_END
+}
+
+int64_t ucdir_noise_loss_workspace_bytes(int64_t B, int64_t per) {
+    if (B < 0 || per < 1) return -1;
+    const int64_t nblk = (per - 1) / LOSS_BLOCK + 1;
+    if (B > 0 && nblk > INT64_MAX / 16 / B) return -1;
+    const int64_t bytes = B * nblk * 16;                     // one (l1, l2) pair of doubles per (sample, block)
+    return bytes > 16 ? bytes : 16;
+}
+
+int32_t ucdir_noise_loss(const float* eps, const float* noise, int64_t B, int64_t per, uint64_t seed, const uint64_t* seeds_dev,
+                         uint32_t step, double* l1, double* l2, void* workspace, int64_t workspace_bytes, void* stream) {
+    API_BEGIN
+    const std::string w("ucdir_noise_loss");
+    require(eps && l1 && l2 && workspace, w + ": null argument (eps, l1, l2 and the workspace are needed)");
+    loss_shape(w, B, per, seeds_dev);
+    require(((uintptr_t)eps & 15) == 0 && ((uintptr_t)noise & 15) == 0 && ((uintptr_t)workspace & 15) == 0,
+            w + ": eps, noise and the workspace must be 16-byte aligned");
+    require(((uintptr_t)l1 & 7) == 0 && ((uintptr_t)l2 & 7) == 0 && ((uintptr_t)seeds_dev & 7) == 0, w + ": l1, l2 and seeds must be 8-byte aligned");
+    const int64_t need = ucdir_noise_loss_workspace_bytes(B, per);
+    require(need > 0 && workspace_bytes >= need, w + ": workspace too small (ucdir_noise_loss_workspace_bytes)");
+    if (B == 0) return 0;
+    const void* others[5] = {noise, seeds_dev, l1, l2, workspace};
+    const char* names[5] = {"noise", "seeds", "l1", "l2", "workspace"};
+    DevGuard dg(same_device(w, eps, "eps", others, names, 5));
+    const long long nblk = (per - 1) / LOSS_BLOCK + 1, units = B * nblk;
+    hipLaunchKernelGGL(noise_loss_kernel, dim3((unsigned)(units < 4096 ? units : 4096)), dim3(256), 0, (hipStream_t)stream, eps, noise, units, nblk,
+                       (long long)per, (unsigned long long)seed, step, (const unsigned long long*)seeds_dev, (double*)workspace);
+    hipLaunchKernelGGL(noise_loss_finish_kernel, dim3((unsigned)(B < 4096 ? B : 4096)), dim3(64), 0, (hipStream_t)stream, (const double*)workspace,
+                       (long long)B, nblk, l1, l2);
     HIPC(hipGetLastError());
     API_END
 }

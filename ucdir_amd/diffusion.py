@@ -3,8 +3,9 @@
 ``GaussianDiffusion`` / ``ResiGaussianGuideDY`` keep the reference's public surface used by
 ``DDPM`` and ``sr.py`` (set_new_noise_schedule, super_resolution, p_sample_loop, p_sample, sample,
 set_loss, registered schedule buffers, ``denoise_fn`` / ``predictor`` / ``pre_initx`` attributes)
-so that ``define_G`` is a drop-in.  Training (``p_losses`` / ``forward``) is outside the scope of
-this build and raises.
+so that ``define_G`` is a drop-in.  ``p_losses`` / ``forward`` evaluate the training loss's forward half - the
+noise-prediction error at drawn noise levels, in eval mode - on the HIP path (``qsample_``, ``noise_loss_``); the backward
+pass, the optimisers, EMA and DDP are outside the scope of this build.
 
 Differences from the reference, all result-preserving:
   * the noise level and the five per-step coefficients are read from host tables (float64 ->
@@ -34,7 +35,7 @@ import torch.nn as nn
 
 from . import dpm_solver as D
 from .ucdir import (FEWSTEP_CLIP, FEWSTEP_FACTORED, UNetSeeInDark, fewstep_threshold_, fewstep_threshold_workspace_bytes, fewstep_update_,
-                    fill_normal_, sampler_step_, sampler_step_rng_)
+                    fill_normal_, noise_loss_, qsample_, sampler_step_, sampler_step_rng_)
 
 SAMPLERS = ("ddpm", "ddim", "dpm_solver++")
 TIME_INPUTS = ("level", "reference")
@@ -460,11 +461,137 @@ class GaussianDiffusion(nn.Module):
     def super_resolution(self, x_in, continous=False):
         return self.p_sample_loop(x_in, continous)
 
-    def p_losses(self, x_in, noise=None):
-        raise NotImplementedError("training is outside the scope of the MI355X sampling build")
+    # ---- the denoising loss, forward half (model/diffusion.py:306-343) -----------------------------------
+    def _level_table(self, level_table=None):
+        prev = self.sqrt_alphas_cumprod_prev if level_table is None else np.asarray(level_table, dtype=np.float64)
+        if prev.ndim != 1 or prev.shape[0] < 2:
+            raise ValueError("level_table must be sqrt(alphas_cumprod) with a leading 1: T + 1 values")
+        return prev
+
+    def draw_levels(self, B, t=None, rng=None, level_table=None):
+        """The reference's two draws (model/diffusion.py:318-325), in its order: ``t = randint(1, T + 1)`` unless given, then
+        ``uniform(prev[t - 1], prev[t], size=B)`` (low > high, as there) rounded to fp32 as ``torch.FloatTensor`` rounds it.
+        ``rng`` defaults to numpy's global generator, so ``np.random.seed(s)`` reproduces the reference's values;
+        ``level_table`` replaces ``sqrt_alphas_cumprod_prev`` (another schedule's table).  Returns ``(t, levels)``, levels fp32 (B,)."""
+        rng = np.random if rng is None else rng
+        prev = self._level_table(level_table)
+        T = prev.shape[0] - 1
+        if t is None:
+            t = rng.randint(1, T + 1)
+        t = int(t)
+        if not 1 <= t <= T:
+            raise ValueError("t must lie in [1, %d], got %d" % (T, t))
+        return t, np.asarray(rng.uniform(prev[t - 1], prev[t], size=int(B)), dtype=np.float64).astype(np.float32)
+
+    @staticmethod
+    def _check_levels(levels, B):
+        lv = np.asarray(levels.detach().cpu().numpy() if torch.is_tensor(levels) else levels, dtype=np.float32).reshape(-1)
+        if lv.shape[0] != B:
+            raise ValueError("levels holds %d values for a batch of %d" % (lv.shape[0], B))
+        if not bool(np.all((lv >= 0) & (lv <= 1))):
+            raise ValueError("noise levels must lie in [0, 1] (sqrt of a cumulative alpha product), got %r" % (lv.tolist(),))
+        return lv
+
+    def _loss_noise(self, x, noise):
+        """The noise of a loss evaluation by the sampler's rules: injected (``noise``, else ``noise_source`` k = 0), else the
+        in-kernel streams at step 0 - the x_T slot - of ``sample_seeds``, of ``noise_seed`` + 1000003 ``noise_index``, or of a
+        fresh key from torch's CPU generator.  Returns the keyword arguments qsample_ and noise_loss_ share."""
+        if noise is None and self.noise_source is not None:
+            noise = self.noise_source(x.shape, x.device, 0)
+        if noise is not None:
+            return {"noise": noise.to(device=x.device, dtype=torch.float32).contiguous(), "seed": 0, "seeds": None, "step": 0}
+        self._start_noise(x.device, kernel_rng=True)
+        return {"noise": None, "seed": self._kseed, "seeds": self._seeds_tensor(x), "step": 0}
+
+    @torch.no_grad()
+    def q_sample(self, x_start, levels, noise=None):
+        """model/diffusion.py:306-313 in one launch (``qsample_``): ``levels`` are B host values in [0, 1]."""
+        x = x_start.contiguous().float()
+        lv = self._check_levels(levels, x.shape[0])
+        try:
+            kw = self._loss_noise(x, noise)
+            return qsample_(x, None, lv, **kw)
+        finally:
+            self._gen = None
+
+    def _x_init(self, sr):
+        """The predictor's output for the residual variants (subtracted from HR, fed to the denoiser as guide); None here."""
+        return None
+
+    @torch.no_grad()
+    def p_losses(self, x_in, noise=None, *, t=None, levels=None, rng=None, level_table=None, per_sample=False, return_parts=False):
+        """The noise-prediction error the reference trains on (model/diffusion.py:315-340), evaluated without a backward pass and
+        in eval mode (the engine has no dropout): one step ``t`` per batch, one level per sample drawn inside the step's interval
+        (``draw_levels``; ``levels`` fixes them and needs no draw), ``x_noisy`` by ``qsample_``, one denoiser call, and the
+        per-sample float64 sums of ``noise_loss_`` - a sample's loss has the same bits in every batch.  The noise follows the
+        sampler's rules (``_loss_noise``).  Returns the batch sum of ``loss_type`` as a 0-d fp32 tensor like the reference's
+        ``reduction='sum'``; ``per_sample``: the (B,) float64 vector; ``return_parts``: additionally a dict of ``t``, ``levels``,
+        ``x_init``, ``x_noisy``, ``eps``, ``l1``, ``l2``.  The trainer's ``l_pix`` is the sum / (B C H W)."""
+        if self.loss_type not in ("l1", "l2"):
+            raise NotImplementedError(self.loss_type)
+        if not self.conditional:
+            raise NotImplementedError("the unconditional loss is not part of the UCDIR restoration path")
+        hr, sr = x_in["HR"], x_in["SR"]
+        if hr.dim() != 4 or tuple(hr.shape) != tuple(sr.shape):
+            raise ValueError("HR %s and SR %s must be (B, C, H, W) of one shape" % (tuple(hr.shape), tuple(sr.shape)))
+        B = hr.shape[0]
+        if levels is not None:                                # every host check precedes the device
+            lv = self._check_levels(levels, B)
+        else:
+            t, lv = self.draw_levels(B, t=t, rng=rng, level_table=level_table)
+        hr, sr = hr.contiguous().float(), sr.contiguous().float()
+        self._begin()
+        try:
+            x_init = self._x_init(sr)
+            kw = self._loss_noise(hr, noise)
+            lvl = torch.from_numpy(lv).to(hr.device)
+            x_noisy = qsample_(hr, x_init, lvl, **kw)
+            eps = self._eps(sr, x_noisy, lvl.view(B, 1), x_init)
+            l1, l2 = noise_loss_(eps.contiguous(), **kw)
+        finally:
+            self._end()
+        mine = l1 if self.loss_type == "l1" else l2
+        ret = mine if per_sample else mine.sum().float()
+        if return_parts:
+            return ret, {"t": t, "levels": lv, "x_init": x_init, "x_noisy": x_noisy, "eps": eps, "l1": l1, "l2": l2}
+        return ret
 
     def forward(self, x, *args, **kwargs):
         return self.p_losses(x, *args, **kwargs)
+
+    @staticmethod
+    def profile_steps(ts, B, draws=1):
+        """The packing of ``loss_profile``: ``len(ts) * draws`` evaluations, B to a forward; sample b of call k takes step
+        ``ts[(k B + b) % len(ts)]``.  Returns one list of B steps per call (the last call wraps round: its surplus samples repeat
+        the first steps and are counted like every other)."""
+        ts = [int(v) for v in ts]
+        if not ts or draws < 1 or B < 1:
+            raise ValueError("loss_profile needs at least one step, one draw and one sample")
+        calls = -(-len(ts) * int(draws) // B)
+        return [[ts[(k * B + b) % len(ts)] for b in range(B)] for k in range(calls)]
+
+    @torch.no_grad()
+    def loss_profile(self, x_in, ts, draws=1, rng=None, level_table=None, return_parts=False):
+        """Mean ``l_pix`` (loss / (C H W)) per step of ``ts``: where along the schedule the network is weak.  Steps are packed B
+        levels to a forward (``profile_steps``) - the denoiser takes one level per sample - so a 16-point profile of one batch of
+        16 is 16 forwards at ``draws=16`` and one at ``draws=1``; each level is drawn inside its step's interval, as
+        ``draw_levels`` draws it.  Returns ``{step: mean l_pix}`` in the order of ``ts``."""
+        rng = np.random if rng is None else rng
+        prev = self._level_table(level_table)
+        B, per = x_in["HR"].shape[0], x_in["HR"][0].numel()
+        tot, cnt, parts = {}, {}, []
+        for steps in self.profile_steps(ts, B, draws):
+            for t in steps:
+                if not 1 <= t <= prev.shape[0] - 1:
+                    raise ValueError("step %d outside [1, %d]" % (t, prev.shape[0] - 1))
+            lv = np.array([rng.uniform(prev[t - 1], prev[t]) for t in steps], dtype=np.float64).astype(np.float32)
+            loss, p = self.p_losses(x_in, levels=lv, per_sample=True, return_parts=True)
+            parts.append((steps, p))
+            for t, v in zip(steps, loss.tolist()):
+                tot[t] = tot.get(t, 0.0) + v / per
+                cnt[t] = cnt.get(t, 0) + 1
+        out = {t: tot[t] / cnt[t] for t in dict.fromkeys(int(v) for v in ts)}
+        return (out, parts) if return_parts else out
 
 
 class ResiGaussianGuideDY(GaussianDiffusion):
@@ -473,6 +600,10 @@ class ResiGaussianGuideDY(GaussianDiffusion):
     def __init__(self, denoise_fn, image_size, channels=3, loss_type="l1", conditional=True, schedule_opt=None):
         super().__init__(denoise_fn, image_size, channels, loss_type, conditional, schedule_opt)
         self.predictor = UNetSeeInDark()
+
+    def _x_init(self, sr):
+        """model/diffusion.py:445-446, 466: x_init = predictor(SR) is subtracted from HR and guides the denoiser."""
+        return self.predictor(sr)
 
     @torch.no_grad()
     def super_resolution(self, x_in, continous=False):

@@ -55,6 +55,11 @@ _SIGS = {
     "ucdir_fewstep_threshold_workspace_bytes": (c_int64, [c_int64]),
     "ucdir_fewstep_threshold": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_float, c_float, c_double, c_float, c_void_p, c_void_p,
                                           c_int64, c_void_p]),
+    "ucdir_qsample": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, ctypes.c_uint64, c_void_p,
+                                ctypes.c_uint32, c_void_p]),
+    "ucdir_noise_loss_workspace_bytes": (c_int64, [c_int64, c_int64]),
+    "ucdir_noise_loss": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, ctypes.c_uint64, c_void_p, ctypes.c_uint32, c_void_p, c_void_p,
+                                   c_void_p, c_int64, c_void_p]),
     "ucdir_gather_windows": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     "ucdir_image_metrics_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "ucdir_image_metrics": (c_int32, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int32, c_int32,

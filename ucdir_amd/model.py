@@ -14,6 +14,7 @@ import logging
 import os
 from collections import OrderedDict
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -82,6 +83,45 @@ class DDPM:
         finally:
             self.netG.sample_seeds = None
         self.SR = out[..., pd:-pd, pd:-pd]
+
+    def val_loss(self, draws=1, ts=None, level_table=None, seed=0):
+        """``l_pix`` - the trainer's log figure, noise-prediction loss / (C H W), model/model.py:104-109 - of every image of the fed
+        batch, on the data as fed (unpadded, as in training) and in eval mode: ``GaussianDiffusion.p_losses`` with one level per image.
+        ``ts`` None: ``draws`` random (step, level) pairs per image, as training draws them; image ``i`` draws from
+        ``numpy.random.RandomState(seed + 1000003 i)`` (``i`` = data["Index"]), so its levels do not depend on the batch.  ``ts``: every
+        image is evaluated ``draws`` times at every step of ``ts``, its level drawn inside the step's interval.  ``level_table``:
+        another schedule's ``sqrt_alphas_cumprod_prev``.  With ``image_seed_base`` set the noise is the in-kernel stream of
+        (image, draw); otherwise the sampler's rules apply.  Returns ``(l_pix, per_step)``: the mean ``l_pix`` per image (a list)
+        and ``{step: [l_pix per image]}`` (empty without ``ts``)."""
+        self.netG.eval()
+        hr = self.data["HR"]
+        B, per = hr.shape[0], hr[0].numel()
+        idxs = _indices(self.data.get("Index"), B)
+        if len(idxs) != B:
+            raise ValueError("data['Index'] must hold one index per image of the batch")
+        prev = self.netG._level_table(level_table)
+        T = prev.shape[0] - 1
+        rngs = [np.random.RandomState((int(seed) + 1000003 * i) % 2 ** 32) for i in idxs]
+        base = getattr(self, "image_seed_base", None)
+        plan = [None] * int(draws) if ts is None else [int(t) for t in ts for _ in range(int(draws))]
+        if not plan:
+            raise ValueError("val_loss needs at least one draw")
+        tot = np.zeros(B)
+        per_step = {}
+        try:
+            for d, t_fixed in enumerate(plan):
+                steps = [r.randint(1, T + 1) if t_fixed is None else t_fixed for r in rngs]
+                lv = np.array([r.uniform(prev[t - 1], prev[t]) for r, t in zip(rngs, steps)], dtype=np.float64).astype(np.float32)
+                if base is not None and per % 4 == 0:         # per-sample streams come in fours
+                    self.netG.sample_seeds = [int(base) + 1000003 * i + 15485863 * (d + 1) for i in idxs]
+                l_pix = self.netG.p_losses({"HR": hr, "SR": self.data["SR"]}, levels=lv, per_sample=True).cpu().numpy() / per
+                tot += l_pix
+                if t_fixed is not None:
+                    acc = per_step.setdefault(t_fixed, np.zeros(B))
+                    acc += l_pix / int(draws)
+        finally:
+            self.netG.sample_seeds = None
+        return (tot / len(plan)).tolist(), {t: v.tolist() for t, v in per_step.items()}
 
     def set_new_noise_schedule(self, schedule_opt, schedule_phase="train"):
         if getattr(self, "schedule_phase", None) != schedule_phase:

@@ -529,6 +529,92 @@ def fill_normal_(x, seed, step=0, seeds=None):
     return x
 
 
+NOISE_LOSS_BLOCK = 4096      # elements of a sample per stage-one partial of noise_loss_ (LOSS_BLOCK of csrc/loss.hip.h)
+
+
+def _loss_noise_args(who, x, seed, seeds, noise):
+    """The (noise pointer, seed, seeds pointer) of qsample_ / noise_loss_ after their shared checks."""
+    if noise is not None:
+        if not (torch.is_tensor(noise) and noise.is_cuda and noise.is_contiguous() and noise.dtype == torch.float32
+                and noise.numel() == x.numel() and noise.device == x.device):
+            raise _lib.UcdirError(who + ": noise must be a contiguous fp32 CUDA tensor shaped like the samples, on their device")
+        seeds = None                                          # injected noise replaces every draw
+    if seeds is not None:
+        _check_seeds(seeds, x, who)
+    null = ctypes.c_void_p(0)
+    return (_ptr(noise) if noise is not None else null, int(seed) & (2 ** 64 - 1), _ptr(seeds) if seeds is not None else null)
+
+
+def qsample_(hr, x_init, levels, out=None, noise_out=None, seed=0, step=0, seeds=None, noise=None):
+    """The fused noising of the denoising loss (csrc/loss.hip.h, ``ucdir_qsample``; model/diffusion.py:306-313):
+    ``x_noisy = c_b x_start + sqrt(1 - c_b^2) z`` with ``x_start = hr - x_init`` (``x_init`` None: ``hr``), every operation rounded
+    to fp32 on its own.  ``hr`` (B, ...) fp32 CUDA; ``levels``: B levels c_b - an fp32 CUDA tensor (read on the device, no host
+    synchronisation, not checked: a level outside [0, 1] gives the reference's NaN) or host values (a sequence, array or CPU
+    tensor), which are refused outside [0, 1].  z is ``noise`` when given, else the ``fill_normal_`` draw of (``seed``, ``step``,
+    element) or, with ``seeds``, of every sample's own stream; ``noise_out`` receives it.  Returns ``out`` (allocated when None)."""
+    L = _lib.load()
+    if not (torch.is_tensor(hr) and hr.is_cuda and hr.is_contiguous() and hr.dtype == torch.float32 and hr.dim() >= 1 and hr.numel() > 0):
+        raise _lib.UcdirError("qsample_ needs a non-empty contiguous fp32 CUDA tensor (B, ...)")
+    B = hr.shape[0]
+
+    def ok(t):
+        return torch.is_tensor(t) and t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and t.numel() == hr.numel() and t.device == hr.device
+    for name, t in (("x_init", x_init), ("out", out), ("noise_out", noise_out)):
+        if t is not None and not ok(t):
+            raise _lib.UcdirError(f"qsample_: {name} must be a contiguous fp32 CUDA tensor shaped like hr on its device")
+    if not (torch.is_tensor(levels) and levels.is_cuda):
+        lv = np.asarray(levels.detach().cpu().numpy() if torch.is_tensor(levels) else levels, dtype=np.float32).reshape(-1)
+        if lv.size != B or not bool(np.all((lv >= 0) & (lv <= 1))):
+            raise _lib.UcdirError("qsample_: levels must be one value in [0, 1] per sample")
+        levels = torch.from_numpy(lv).to(hr.device)
+    if not (levels.device == hr.device and levels.dtype == torch.float32 and levels.is_contiguous() and levels.numel() == B):
+        raise _lib.UcdirError("qsample_: levels must be a contiguous fp32 tensor with one entry per sample, on the device of hr")
+    nz, seed, sd = _loss_noise_args("qsample_", hr, seed, seeds, noise)
+    if out is None:
+        out = torch.empty_like(hr)
+    # the header's contract: an output shares no storage with an input or with the other output
+    for name, o in (("out", out), ("noise_out", noise_out)):
+        for other in (hr, x_init, noise, noise_out if o is out else out):
+            if o is not None and other is not None and o.data_ptr() == other.data_ptr():
+                raise _lib.UcdirError(f"qsample_: {name} may not alias an input or the other output")
+    null = ctypes.c_void_p(0)
+    _lib.check(L.ucdir_qsample(_ptr(hr), _ptr(x_init) if x_init is not None else null, _ptr(levels), _ptr(out),
+                               _ptr(noise_out) if noise_out is not None else null, nz, B, hr.numel() // B, seed, sd, int(step),
+                               _stream_ptr(hr.device)))
+    return out
+
+
+def noise_loss_workspace_bytes(B, per):
+    """Bytes of workspace ``noise_loss_`` needs for ``B`` samples of ``per`` elements (a host query; -1 on a bad shape)."""
+    return int(_lib.load().ucdir_noise_loss_workspace_bytes(int(B), int(per)))
+
+
+def noise_loss_(eps, seed=0, step=0, seeds=None, noise=None, out=None, workspace=None):
+    """Per-sample noise-prediction error (csrc/loss.hip.h, ``ucdir_noise_loss``): ``l1[b] = sum |z - eps|`` and
+    ``l2[b] = sum fl32((z - eps)^2)`` over sample b of ``eps`` (B, ...) fp32 CUDA, fp32 terms summed in float64 in an order that
+    depends on the sample's size alone: a sample's pair has the same bits in every batch and on every call.  z is ``noise`` when
+    given, else regenerated from (``seed`` | ``seeds``, ``step``, element) exactly as ``qsample_`` / ``fill_normal_`` draw it.
+    Returns ``(l1, l2)``, float64 (B,) views of ONE buffer of 2 B doubles (``out`` when given), so one copy brings both to the host."""
+    L = _lib.load()
+    if not (torch.is_tensor(eps) and eps.is_cuda and eps.is_contiguous() and eps.dtype == torch.float32 and eps.dim() >= 1 and eps.numel() > 0):
+        raise _lib.UcdirError("noise_loss_ needs a non-empty contiguous fp32 CUDA tensor (B, ...)")
+    B, per = eps.shape[0], eps.numel() // eps.shape[0]
+    nz, seed, sd = _loss_noise_args("noise_loss_", eps, seed, seeds, noise)
+    if out is None:
+        out = torch.empty(2 * B, dtype=torch.float64, device=eps.device)
+    elif not (torch.is_tensor(out) and out.device == eps.device and out.dtype == torch.float64 and out.is_contiguous() and out.numel() == 2 * B):
+        raise _lib.UcdirError("noise_loss_: out must be a contiguous float64 tensor of 2 B elements on the device of eps")
+    need = noise_loss_workspace_bytes(B, per)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=eps.device)
+    elif not (torch.is_tensor(workspace) and workspace.device == eps.device and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
+        raise _lib.UcdirError("noise_loss_: workspace must be a contiguous uint8 CUDA tensor on the device of eps")
+    l1, l2 = out[:B], out[B:]
+    _lib.check(L.ucdir_noise_loss(_ptr(eps), nz, B, per, seed, sd, int(step), _ptr(l1), _ptr(l2), _ptr(workspace), workspace.numel(),
+                                  _stream_ptr(eps.device)))
+    return l1, l2
+
+
 class UNetSeeInDark(nn.Module):
     """Initial-restoration predictor (model/ucdir.py:310-416) on the HIP engine; parameter names and
     shapes match the reference, there is no PyTorch forward."""
